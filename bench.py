@@ -1,14 +1,18 @@
 """Benchmark of the XMC-GAN G+D training iteration on MI355X (metric and configs: BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload headline|magp|config2|config3]
-                    [--imsize 256 --batch B --cfg df_gan_damsm_nomagp.yml]
+                    [--imsize 256 --batch B --cfg df_gan_damsm_nomagp.yml] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one full iteration of the reference loop body (train_gan.py:185-291: D step, optional MA-GP, G step,
 both Adam updates) on one synthetic COCO-shaped batch that is already resident in HBM.  One process per GPU;
-weak scaling (per-GPU batch fixed); value = images of all ranks / max-over-ranks time.  Rank 0 prints ONE JSON line
-carrying, besides the throughput:
+weak scaling (per-GPU batch fixed); value = images of all ranks / max-over-ranks time.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the throughput with `ms_per_step` (wall time of the K steps / K),
+`step_ms` and `dist`.  `--dump-outputs DIR` writes what the last timed step returned (its losses and generated images) as
+DIR/<name>.npy in float32 (the images: a fixed, seeded sample of FAKE_SAMPLE elements); the inputs and initial weights are
+seeded and that last step starts from the initial training state, so that runs and builds can be compared output for output.  `--full` adds the side measurements below, each of which costs runs of its own (a leg
+is dropped again by its `--no_<leg>` flag):
   roofline      the dominant kernel (MFMA view), timed per launch with HIP events on the launch stream
   roofline_hbm  the bandwidth-bound convolution kernels (algorithmic intensity below the chip's ridge): GB/s against 8 TB/s
   cpu_baseline  the CPU oracle timed on this host's cores
@@ -46,6 +50,7 @@ G_IN_GFLOP = {64: 1.632, 128: 6.536, 256: 26.150}         # CONCEPT_IN_DF_GEN
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0          # HBM3E spec (MI355X_MICROARCH.md; ~6300 measured with a float4 copy)
+FAKE_SAMPLE = 1 << 22          # --dump-outputs: generated-image elements kept (16 MB as float32; the headline batch has 50 M)
 
 
 # named workloads (BASELINE.json `configs`; the default is the single-GPU leg of configs 4/5, the one `metric` is quoted on)
@@ -81,7 +86,15 @@ def parse():
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_roofline", action="store_true")
     ap.add_argument("--no_entrypoint", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side legs: roofline, cpu_baseline, alt_precision, entrypoint, parity (off: the headline only)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.no_roofline = a.no_cpu_baseline = a.no_alt_precision = a.no_entrypoint = a.no_parity = True
     w = WORKLOADS[a.workload]
     a.imsize = w["imsize"] if a.imsize is None else a.imsize
     a.batch = w["batch"] if a.batch is None else a.batch
@@ -230,7 +243,7 @@ def alt_precision_leg(a):
     """The timed workload once more in the IEEE-half mode (a child process: a fresh allocator, graph pool and library state)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup),
-           "--imsize", str(a.imsize), "--batch", str(a.batch), "--cfg", a.cfg, "--precision", "f16", "--no_cpu_baseline",
+           "--imsize", str(a.imsize), "--batch", str(a.batch), "--cfg", a.cfg, "--precision", "f16", "--full", "--no_cpu_baseline",
            "--no_parity", "--no_alt_precision", "--no_entrypoint"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -270,6 +283,54 @@ def entrypoint_leg(a):
                 steps=thr.get("steps"), hipgraph=thr.get("hipgraph"),
                 note="loader batches are host tensors (pinned, uploaded on a side stream while the previous iteration runs); includes the "
                      "text encoder's forward and the CPU-side noise draw of every iteration (train_gan.py:160-170,197)")
+
+
+def dump_outputs(out, path):
+    """`out` (the dict a G+D iteration returns: 0-d losses and `fake`, the generated images) as path/<name>.npy in float32.
+    `fake` is reduced to FAKE_SAMPLE elements at flat positions drawn from a fixed seed, the same positions in every run of a
+    workload, so that the files stay small.  The inputs and the initial weights are seeded, and the last timed step of a
+    dumping run starts from that initial state (restore_training_state): the order of f32 atomics is not seeded, and a few
+    dozen Adam steps of the GAN amplify it (without the restore, two runs of one build end 25 steps later with image samples
+    that correlate to 0.85)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        v = v.detach().float()
+        if k == "fake" and v.numel() > FAKE_SAMPLE:
+            idx = torch.randint(0, v.numel(), (FAKE_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        np.save(os.path.join(path, f"{k}.npy"), v.cpu().numpy())
+
+
+def snapshot_training_state(nets):
+    """copies of every parameter and buffer of `nets` (the seeded initial state: no optimizer step has run yet)"""
+    return [(t, t.detach().clone()) for net in nets for t in list(net.parameters()) + list(net.buffers())]
+
+
+def restore_training_state(snap, opts, it_states, dev):
+    """Put the training state back where `snap` was taken, as the optimizer itself writes it: the tensors in place behind
+    autograd's back (a captured graph keeps their addresses), their packed copies re-packed (ops.repack_params), the Adam
+    moments and step counters zeroed (= not yet created), the critic counters and the IEEE-half loss scales at their start."""
+    from xmc_gan_amd import ops
+    from xmc_gan_amd.ops import _config
+    with torch.no_grad():
+        for t, s in snap:
+            t.data.copy_(s)
+        params = [t for t, _ in snap if isinstance(t, torch.nn.Parameter)]
+        for p in params:
+            p._xmc_epoch = getattr(p, "_xmc_epoch", 0) + 1
+        ops.repack_params(params)
+        for opt in opts:
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+        for sc in _config._scalers.values():
+            fresh = _config.LossScaler(dev)
+            sc.sf.copy_(fresh.sf)
+            sc.si.copy_(fresh.si)
+    for st in it_states:
+        st.clear()
 
 
 def self_launch(n):
@@ -363,6 +424,10 @@ def main():
             if n_.endswith("gamma"):
                 p_.fill_(0.1)
 
+    # --dump-outputs: the last timed step starts again from this seeded initial state, so that what it computes does not
+    # carry the unordered f32 atomics of every step before it, amplified by training (restore_training_state)
+    snap = snapshot_training_state((netG, netD)) if a.dump_outputs else None
+
     B, S, E, T = a.batch, a.imsize, cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH
     g = torch.Generator().manual_seed(100 + rank)
     nb = 4                                                    # a few distinct resident batches, cycled
@@ -425,6 +490,8 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(a.steps):
+        if snap is not None and i == a.steps - 1:
+            restore_training_state(snap, (optG, optD), [state] + ([graphed.it_state] if graphed is not None else []), dev)
         last = step(a.warmup + i)
         marks[i + 1].record()
     barrier()
@@ -435,6 +502,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     finite = all(torch.isfinite(v).all().item() for k, v in last.items() if k != "fake")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(last, a.dump_outputs)
 
     roof = roof_hbm = None
     if not a.no_roofline:
@@ -490,7 +559,7 @@ def main():
         if not a.no_cpu_baseline and world == 1:       # the CPU leg is timed on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(cfg, a.cfg, S)
     # free the timed run's networks, graphs and pools before the side legs
-    del graphed, netG, netD, optG, optD, data, last
+    del graphed, netG, netD, optG, optD, data, last, snap
     import gc
     gc.collect()
     torch.cuda.empty_cache()

@@ -20,14 +20,16 @@ import tempfile
 import types
 
 import numpy as np
-import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import pinned_cpu  # noqa: E402
+pinned_cpu.pin_env()     # the arithmetic the tests recompute the fixtures with (pinned_cpu.py), before torch runs a kernel
+import torch  # noqa: E402
 import ref_harness as RH  # noqa: E402
 import xmc_ref as X      # noqa: E402
 
-torch.set_num_threads(8)
+torch.set_num_threads(pinned_cpu.THREADS)
 
 
 def stats(t):
@@ -273,48 +275,53 @@ def main():
         for fn in ("golden_forward", "golden_step", "golden_rnn_encoder"):
             g[fn] = (lambda f: (lambda name, *args, **kw: f(name, *args, **kw) if a.only in name else None))(g[fn])
         g["golden_labels"] = (lambda f: (lambda *args, **kw: f(*args, **kw) if a.only in "labels" else None))(g["golden_labels"])
+    with pinned_cpu.no_onednn():
+        generate(a.out)
+
+
+def generate(out):
     N8 = {"TRAIN.NCH": 8}
-    golden_labels(a.out)
-    golden_forward("df64_nch32", "df_gan_damsm.yml", 2, 11, a.out)
-    golden_forward("df128_nch8", "df_gan_damsm.yml", 2, 12, a.out, **{"IMG.SIZE": 128, **N8})
-    golden_forward("df256_nch8", "df_gan_sbert_damsm_nomagp.yml", 2, 13, a.out, **{"IMG.SIZE": 256, **N8})
-    golden_forward("sep64_nch8", "df_gan_sbert_seperate.yml", 2, 14, a.out, **N8)
+    golden_labels(out)
+    golden_forward("df64_nch32", "df_gan_damsm.yml", 2, 11, out)
+    golden_forward("df128_nch8", "df_gan_damsm.yml", 2, 12, out, **{"IMG.SIZE": 128, **N8})
+    golden_forward("df256_nch8", "df_gan_sbert_damsm_nomagp.yml", 2, 13, out, **{"IMG.SIZE": 256, **N8})
+    golden_forward("sep64_nch8", "df_gan_sbert_seperate.yml", 2, 14, out, **N8)
     # df_gan_sbert.yml / concept_in_df_gan_sbert.yml cannot run in the reference itself: with E=768 != NEF and
     # neither IMG_MATCH/SENT_MATCH/SEPERATE, D_GET_LOGITS sizes joint_conv for text_dim (df_gan.py:152-157)
     # while train() feeds it netG.proj_sent(sent) of width NEF (train_gan.py:191) -> channel mismatch.
-    golden_forward("nomatch64_nch8", "concept_in_df_gan.yml", 2, 15, a.out, **N8)
-    golden_forward("cin64_nch8", "concept_in_df_gan_damsm_nomagp.yml", 2, 16, a.out, **N8)
-    golden_forward("cin128_nch8", "concept_in_df_gan_sbert_n2_damsm.yml", 1, 17, a.out, **{"IMG.SIZE": 128, **N8})
-    golden_forward("cout64_nch8", "concept_out_df_gan_sbert_damsm_nomagp.yml", 2, 18, a.out, **N8)
-    golden_forward("cout64_nonorm", "concept_out_df_gan_sbert_damsm_nomagp.yml", 2, 19, a.out,
+    golden_forward("nomatch64_nch8", "concept_in_df_gan.yml", 2, 15, out, **N8)
+    golden_forward("cin64_nch8", "concept_in_df_gan_damsm_nomagp.yml", 2, 16, out, **N8)
+    golden_forward("cin128_nch8", "concept_in_df_gan_sbert_n2_damsm.yml", 1, 17, out, **{"IMG.SIZE": 128, **N8})
+    golden_forward("cout64_nch8", "concept_out_df_gan_sbert_damsm_nomagp.yml", 2, 18, out, **N8)
+    golden_forward("cout64_nonorm", "concept_out_df_gan_sbert_damsm_nomagp.yml", 2, 19, out,
                    **{"GEN.NORMALIZE": False, **N8})
-    golden_step("df64_magp", "df_gan_damsm.yml", 4, 2, 21, a.out, **N8)
-    golden_step("df64_nomagp", "df_gan_damsm_nomagp.yml", 4, 2, 22, a.out, **N8)
-    golden_step("df64_sep", "df_gan_sbert_seperate.yml", 3, 2, 23, a.out, **N8)
-    golden_step("df64_ncrit2", "concept_in_df_gan_sbert_n2_damsm.yml", 3, 2, 24, a.out, **N8)
-    golden_step("cout64", "concept_out_df_gan_sbert_damsm_nomagp.yml", 3, 1, 25, a.out, **N8)
-    golden_step("df128_nomagp", "df_gan_damsm_nomagp.yml", 2, 1, 26, a.out, **{"IMG.SIZE": 128, **N8})
+    golden_step("df64_magp", "df_gan_damsm.yml", 4, 2, 21, out, **N8)
+    golden_step("df64_nomagp", "df_gan_damsm_nomagp.yml", 4, 2, 22, out, **N8)
+    golden_step("df64_sep", "df_gan_sbert_seperate.yml", 3, 2, 23, out, **N8)
+    golden_step("df64_ncrit2", "concept_in_df_gan_sbert_n2_damsm.yml", 3, 2, 24, out, **N8)
+    golden_step("cout64", "concept_out_df_gan_sbert_damsm_nomagp.yml", 3, 1, 25, out, **N8)
+    golden_step("df128_nomagp", "df_gan_damsm_nomagp.yml", 2, 1, 26, out, **{"IMG.SIZE": 128, **N8})
     # DISC.SPEC_NORM: True (config/gan.py:62 default): weight_orig / weight_u / weight_v keys, one power
     # iteration per forward call
     SN = {"DISC.SPEC_NORM": True, **N8}
-    golden_forward("sn64_nch8", "df_gan_damsm.yml", 2, 31, a.out, **SN)
-    golden_step("sn64_nomagp", "df_gan_damsm_nomagp.yml", 4, 2, 32, a.out, **SN)
-    golden_step("sn64_magp", "df_gan_damsm.yml", 3, 1, 33, a.out, **SN)
+    golden_forward("sn64_nch8", "df_gan_damsm.yml", 2, 31, out, **SN)
+    golden_step("sn64_nomagp", "df_gan_damsm_nomagp.yml", 4, 2, 32, out, **SN)
+    golden_step("sn64_magp", "df_gan_damsm.yml", 3, 1, 33, out, **SN)
     # word-attention generator concept_gan.OutNetG: BatchNorm blocks + word<->concept attention with mask
     WG = {"GEN.ENCODER_NAME": "CONCEPT_OUTATTN_GEN", **N8}
-    golden_forward("wordg64_nch8", "df_gan_damsm_nomagp.yml", 3, 51, a.out, **WG)
-    golden_forward("wordg128_nonorm", "df_gan_sbert_damsm_nomagp.yml", 2, 52, a.out, **{"IMG.SIZE": 128, "GEN.NORMALIZE": False, **WG})
-    golden_step("wordg64", "df_gan_damsm_nomagp.yml", 4, 2, 53, a.out, **WG)
+    golden_forward("wordg64_nch8", "df_gan_damsm_nomagp.yml", 3, 51, out, **WG)
+    golden_forward("wordg128_nonorm", "df_gan_sbert_damsm_nomagp.yml", 2, 52, out, **{"IMG.SIZE": 128, "GEN.NORMALIZE": False, **WG})
+    golden_step("wordg64", "df_gan_damsm_nomagp.yml", 4, 2, 53, out, **WG)
     # the word-REGION attention generator concept_gan.InNetG, repaired: repaired_word_in_netg above
     WI = {"GEN.ENCODER_NAME": "CONCEPT_INATTN_GEN", **N8}
-    golden_forward("wordin64_nch8", "df_gan_damsm_nomagp.yml", 3, 61, a.out, **WI)
-    golden_forward("wordin128_nonorm", "df_gan_sbert_damsm_nomagp.yml", 2, 62, a.out, **{"IMG.SIZE": 128, "GEN.NORMALIZE": False, **WI})
-    golden_step("wordin64", "df_gan_damsm_nomagp.yml", 4, 2, 63, a.out, **WI)
+    golden_forward("wordin64_nch8", "df_gan_damsm_nomagp.yml", 3, 61, out, **WI)
+    golden_forward("wordin128_nonorm", "df_gan_sbert_damsm_nomagp.yml", 2, 62, out, **{"IMG.SIZE": 128, "GEN.NORMALIZE": False, **WI})
+    golden_step("wordin64", "df_gan_damsm_nomagp.yml", 4, 2, 63, out, **WI)
     # frozen text front end: embedding + bidirectional LSTM over packed captions
-    golden_rnn_encoder("enc_damsm", "df_gan_damsm.yml", 6, 41, a.out)
-    golden_rnn_encoder("enc_len12", "df_gan_damsm.yml", 5, 42, a.out, **{"TEXT.MAX_LENGTH": 12, "TEXT.VOCA_SIZE": 500})
+    golden_rnn_encoder("enc_damsm", "df_gan_damsm.yml", 6, 41, out)
+    golden_rnn_encoder("enc_len12", "df_gan_damsm.yml", 5, 42, out, **{"TEXT.MAX_LENGTH": 12, "TEXT.VOCA_SIZE": 500})
     # the GRU branch of the same encoder (encoder.py:99-102; no shipped preset selects it)
-    golden_rnn_encoder("enc_gru", "df_gan_damsm.yml", 5, 43, a.out, **{"TEXT.RNN_TYPE": "GRU", "TEXT.VOCA_SIZE": 400})
+    golden_rnn_encoder("enc_gru", "df_gan_damsm.yml", 5, 43, out, **{"TEXT.RNN_TYPE": "GRU", "TEXT.VOCA_SIZE": 400})
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02prof
 mkdir -p $O
-rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py > $O/bench_under_rocprof.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --full > $O/bench_under_rocprof.json 2> $O/stats.err
 python profiles/summarize.py stats $O/stats $O/r02_kernel_stats_256px_b256.csv
 rm -rf $O/stats
 echo stats done

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:?}"
 O=gpurun_out/r04prof
 mkdir -p $O
-rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --no_alt_precision --no_entrypoint --no_parity > $O/r04_bench_under_rocprof_256px_b256.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --full --no_alt_precision --no_entrypoint --no_parity > $O/r04_bench_under_rocprof_256px_b256.json 2> $O/stats.err
 python profiles/summarize.py stats $O/stats $O/r04_kernel_stats_256px_b256.csv
 rm -rf $O/stats
 echo stats done

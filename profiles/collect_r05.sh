@@ -6,9 +6,9 @@ cd "${GRAFT_REPO_ROOT:?}"
 O=gpurun_out/r05prof
 mkdir -p $O
 Q="--no_alt_precision --no_entrypoint --no_parity"
-python bench.py > $O/r05_bench_default_256px_b256.json 2> $O/bench.err
+python bench.py --full > $O/r05_bench_default_256px_b256.json 2> $O/bench.err
 echo bench done
-rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py $Q > $O/r05_bench_under_rocprof_256px_b256.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --full $Q > $O/r05_bench_under_rocprof_256px_b256.json 2> $O/stats.err
 python profiles/summarize.py stats $O/stats $O/r05_kernel_stats_256px_b256.csv
 rm -rf $O/stats
 rocprofv3 --kernel-trace --stats -f csv -d $O/stats16 -- python bench.py $Q --precision f16 --no_cpu_baseline --no_roofline > $O/r05_bench_under_rocprof_f16.json 2> $O/stats16.err

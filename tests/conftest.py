@@ -25,4 +25,9 @@ def _usable_cores():
 
 def pytest_sessionstart(session):
     import torch
+    if not torch.cuda.is_available():
+        # the CPU tests compare the oracle with tests/golden/*.npz on host-independent code paths (oracle/pinned_cpu.py), set
+        # before torch runs a kernel.  Not beside the GPU: the GPU parity bars were measured against the oracle's default paths.
+        import pinned_cpu
+        pinned_cpu.pin_env()
     torch.set_num_threads(_usable_cores())      # the CPU oracle must not oversubscribe a container with a CPU quota

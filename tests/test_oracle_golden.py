@@ -4,10 +4,18 @@ import numpy as np
 import pytest
 import torch
 
+import pinned_cpu
 import xmc_ref as X
 from golden_util import fixtures, hyper_for, load, stats
 
-torch.set_num_threads(4)
+torch.set_num_threads(pinned_cpu.THREADS)
+
+
+@pytest.fixture(autouse=True)
+def _pinned_arithmetic():
+    """the code paths oracle/make_golden.py recorded the fixtures with (oracle/pinned_cpu.py)"""
+    with pinned_cpu.no_onednn():
+        yield
 
 
 def _close(a, b, rtol=2e-4, atol=2e-5):
