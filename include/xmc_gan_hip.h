@@ -507,6 +507,41 @@ int xmc_adam_step_scaled(const XmcAdamEntry* table_dev, int ntensors, const int3
                          float lr, float beta1, float beta2, float eps, float* scale_dev, int32_t* flags_dev,
                          int mode, float growth, float backoff, int interval, void* stream);
 
+/*
+ * Exponential moving average of a network's weights (the "shadow" set a GAN is sampled from at evaluation time; the reference
+ * has none).  Per element, once per APPLIED optimizer step:
+ *     d = 0 while *num_updates_dev < start (warm-up: the shadow becomes a bit-exact copy of the weight), else decay
+ *     e = e + (1 - d) * (p - e)            (f32; an element with e == p is a fixed point, bit for bit)
+ * `num_updates_dev` is ONE device int32 for the whole shadow set, the number of updates already applied; warm-up or averaging
+ * is decided on the device from it, so a captured call crosses `start` without re-capture.  `table_dev` is a DEVICE array of
+ * ntensors entries, `chunks_dev` the (tensor index, chunk index) list of xmc_adam_step.  Tensors may start at any 4-byte
+ * aligned address (16-byte accesses are taken only where every pointer of a chunk is 16-byte aligned) and have any length.
+ * Rejected with XMC_EINVAL before anything is launched: NULL tables or counter, counts < 1, decay outside [0, 1), start < 0.
+ *
+ * xmc_ema_step: reads param, reads and writes shadow, for every tensor of the table, in one launch; `bump` != 0: then
+ * *num_updates_dev += 1 (a caller that covers one shadow set with several calls bumps in the last one).  `skip_flag_dev`
+ * (NULL: none) is the found-inf flag of a loss scaler: while it is up NOTHING is written, the counter included.
+ */
+typedef struct XmcEmaEntry {
+    float* shadow;
+    const float* param;
+    int64_t n;
+} XmcEmaEntry;
+int xmc_ema_step(const XmcEmaEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks, float decay, int start,
+                 int32_t* num_updates_dev, const int32_t* skip_flag_dev, int bump, void* stream);
+/* xmc_adam_step / xmc_adam_step_scaled with the shadow update fused into the Adam update (the new weight is averaged while it
+ * is in registers: 8 instead of 12 bytes of extra traffic per element).  `ema_table_dev` is parallel to `table_dev` (same
+ * tensors, same order); only its `shadow` is read, NULL = that tensor has no shadow.  Weights, moments and step counters end up
+ * bit-identical to those of the entry points above.  Under the loss scale, while the found-inf flag is up NOTHING moves:
+ * weights, moments, step counters, shadow, *num_updates_dev. */
+int xmc_adam_ema_step(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors, const int32_t* chunks_dev,
+                      int nchunks, float lr, float beta1, float beta2, float eps, float grad_scale, float decay, int start,
+                      int32_t* num_updates_dev, int bump, void* stream);
+int xmc_adam_ema_step_scaled(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
+                             const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
+                             float* scale_dev, int32_t* flags_dev, int mode, float growth, float backoff, int interval,
+                             float decay, int start, int32_t* num_updates_dev, int bump, void* stream);
+
 /* ---- matching-aware gradient penalty, train_gan.py:241-247:  2 * mean_b ||[d logit / d img_b, d logit / d sent_b]||_2^6 ---------
  * ss[b] += sum_k x[b][k]^2 over an f32 block [B, cols] (cols % 4 == 0; ss zeroed by the caller, blocks accumulate);
  * gp = mean_b ss[b]^3 and coef[b] = 6 ss[b]^2 / B (so that d gp / d x[b][k] = coef[b] * x[b][k]);

@@ -2,6 +2,7 @@
 // (torch.optim.Adam.step at train_gan.py:229,252,289: eps 1e-8, no weight decay, no amsgrad).
 // The table lives in device memory and is static while the parameter/gradient storage is, so the
 // launch is hipGraph-capturable; per-tensor step counters are kept on the device as well.
+// Second half of the file: the exponential moving average of the weights, on its own and fused into the Adam update.
 #include "common.h"
 
 namespace {
@@ -115,6 +116,171 @@ extern "C" int xmc_adam_step_scaled(const XmcAdamEntry* table_dev, int ntensors,
         hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ch, lr, beta1, beta2, eps, 1.f, (const float*)scale_dev,
                            (const int*)flags_dev);
         hipLaunchKernelGGL(adam_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)flags_dev);
+    }
+    if (mode & XMC_ADAM_RESCALE) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, scale_dev, flags_dev, growth, backoff, interval);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Exponential moving average of the weights (the shadow set a GAN is sampled from at evaluation time), once per APPLIED
+// optimizer step:  e += (1 - d) * (p - e)  with d = 0 while fewer than `start` updates have been applied (then e = p, a bit-exact
+// copy) and d = decay afterwards.  The number of applied updates is ONE device counter for the whole shadow set and the choice
+// is made here from it, so a captured graph crosses `start` without re-capture.  The (p - e) form makes e == p a fixed point.
+// Unlike adam_kernel above these kernels take 16-byte accesses only where every pointer they dereference is 16-byte aligned
+// (chunks start at multiples of CHUNK elements, so a chunk is aligned exactly when its tensors' bases are) and finish a
+// vectorised body with a scalar tail, so tensors carved from a flat buffer at any element offset are handled.
+namespace {
+__device__ __forceinline__ bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+__device__ __forceinline__ float ema_elem(float e, float p, float w, bool copy) { return copy ? p : __builtin_fmaf(w, p - e, e); }
+
+__global__ void ema_kernel(const XmcEmaEntry* __restrict__ tab, const int2* __restrict__ chunks, float decay, int start,
+                           const int* __restrict__ nupd, const int* __restrict__ si) {
+    if (si && *si) return;                      // the optimizer step this update belongs to is skipped: the shadow stays
+    const int2 c = chunks[blockIdx.x];
+    const XmcEmaEntry t = tab[c.x];
+    const bool copy = *nupd < start;
+    const float w = 1.f - decay;
+    const int64_t base = (int64_t)c.y * CHUNK;
+    const int lim = (int)(t.n - base < CHUNK ? t.n - base : CHUNK);
+    float* e = t.shadow + base; const float* p = t.param + base;
+    int body = 0;
+    if (aligned16(e) && aligned16(p)) {
+        body = lim & ~3;
+        for (int i = threadIdx.x * 4; i < body; i += NT * 4) {
+            f32x4 E = *reinterpret_cast<f32x4*>(e + i);
+            const f32x4 P = *reinterpret_cast<const f32x4*>(p + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) E[k] = ema_elem(E[k], P[k], w, copy);
+            *reinterpret_cast<f32x4*>(e + i) = E;
+        }
+    }
+    for (int i = body + threadIdx.x; i < lim; i += NT) e[i] = ema_elem(e[i], p[i], w, copy);
+}
+
+// adam_kernel's update with the shadow update applied to the new weight while it is in registers: 8 bytes of extra traffic per
+// element instead of the 12 of a pass of its own.  The weights, moments and counters it leaves are bit-identical to
+// adam_kernel's.  That takes care: as compiled, adam_kernel's two paths round the moment updates differently -- its 16-byte path
+// (tensors with n % 4 == 0) contracts `b * m + t` into one FMA, its scalar path (all other tensors) rounds product and sum
+// separately -- so the arithmetic is written out here, contraction off, in both forms, and a tensor gets the form adam_kernel
+// gives it (by n % 4), whichever way this kernel accesses its memory.  ema[c.x].shadow == NULL: that tensor has no shadow.
+template <bool FMA>
+__device__ __forceinline__ float adam_elem(float P, float G, float& M, float& V, float b1, float b2, float step_size, float bc2s,
+                                           float eps) {
+#pragma clang fp contract(off)
+    const float t = (1.f - b1) * G, u = ((1.f - b2) * G) * G;
+    M = FMA ? __builtin_fmaf(b1, M, t) : b1 * M + t;
+    V = FMA ? __builtin_fmaf(b2, V, u) : b2 * V + u;
+    return P - (step_size * M) / (sqrtf(V) / bc2s + eps);
+}
+
+template <bool FMA>
+__device__ __forceinline__ void adam_ema_chunk(float* p, const float* g, float* m, float* v, float* sh, int lim, float gs, float b1,
+                                               float b2, float step_size, float bc2s, float eps, float w, bool copy) {
+    int body = 0;
+    if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(sh)) {
+        body = lim & ~3;
+        for (int i = threadIdx.x * 4; i < body; i += NT * 4) {
+            f32x4 P = *reinterpret_cast<f32x4*>(p + i), G = *reinterpret_cast<const f32x4*>(g + i);
+            f32x4 M = *reinterpret_cast<f32x4*>(m + i), V = *reinterpret_cast<f32x4*>(v + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float Mk = M[k], Vk = V[k];
+                P[k] = adam_elem<FMA>(P[k], G[k] * gs, Mk, Vk, b1, b2, step_size, bc2s, eps);
+                M[k] = Mk; V[k] = Vk;
+            }
+            *reinterpret_cast<f32x4*>(p + i) = P; *reinterpret_cast<f32x4*>(m + i) = M; *reinterpret_cast<f32x4*>(v + i) = V;
+            if (sh) {
+                f32x4 E = *reinterpret_cast<f32x4*>(sh + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) E[k] = ema_elem(E[k], P[k], w, copy);
+                *reinterpret_cast<f32x4*>(sh + i) = E;
+            }
+        }
+    }
+    for (int i = body + threadIdx.x; i < lim; i += NT) {
+        float M = m[i], V = v[i];
+        const float P = adam_elem<FMA>(p[i], g[i] * gs, M, V, b1, b2, step_size, bc2s, eps);
+        p[i] = P; m[i] = M; v[i] = V;
+        if (sh) sh[i] = ema_elem(sh[i], P, w, copy);
+    }
+}
+
+__global__ void adam_ema_kernel(const XmcAdamEntry* __restrict__ tab, const XmcEmaEntry* __restrict__ ema,
+                                const int2* __restrict__ chunks, float lr, float b1, float b2, float eps, float gs,
+                                const float* __restrict__ sf, const int* __restrict__ si, float decay, int start,
+                                const int* __restrict__ nupd) {
+    if (si && *si) return;                      // a non-finite gradient: the whole step is skipped, shadow included
+    if (sf) gs *= sf[1];
+    const int2 c = chunks[blockIdx.x];
+    const XmcAdamEntry t = tab[c.x];
+    const int step = *t.step + 1;
+    const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
+    const float step_size = lr / bc1;
+    const bool copy = *nupd < start;
+    const float w = 1.f - decay;
+    const int64_t base = (int64_t)c.y * CHUNK;
+    const int lim = (int)(t.n - base < CHUNK ? t.n - base : CHUNK);
+    float* sh = ema[c.x].shadow;
+    if (sh) sh += base;
+    if ((t.n & 3) == 0) adam_ema_chunk<true>(t.param + base, t.grad + base, t.m + base, t.v + base, sh, lim, gs, b1, b2, step_size, bc2s, eps, w, copy);
+    else adam_ema_chunk<false>(t.param + base, t.grad + base, t.m + base, t.v + base, sh, lim, gs, b1, b2, step_size, bc2s, eps, w, copy);
+}
+
+// after all tensors: the per-tensor Adam counters (tab == NULL: none) and, with `bump`, the shadow set's one counter
+__global__ void ema_bump_kernel(const XmcAdamEntry* tab, int n, const int* __restrict__ si, int* nupd, int bump) {
+    if (si && *si) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tab && i < n) *tab[i].step += 1;
+    if (bump && i == 0) *nupd += 1;
+}
+
+bool ema_args_ok(float decay, int start, const int32_t* nupd) { return nupd && decay >= 0.f && decay < 1.f && start >= 0; }
+}  // namespace
+
+extern "C" int xmc_ema_step(const XmcEmaEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks, float decay,
+                            int start, int32_t* num_updates_dev, const int32_t* skip_flag_dev, int bump, void* stream) {
+    if (!table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !ema_args_ok(decay, start, num_updates_dev)) return XMC_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(ema_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, reinterpret_cast<const int2*>(chunks_dev), decay, start,
+                       (const int*)num_updates_dev, (const int*)skip_flag_dev);
+    if (bump)
+        hipLaunchKernelGGL(ema_bump_kernel, dim3(1), dim3(64), 0, st, (const XmcAdamEntry*)nullptr, 0, (const int*)skip_flag_dev,
+                           (int*)num_updates_dev, 1);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xmc_adam_ema_step(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
+                                 const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
+                                 float grad_scale, float decay, int start, int32_t* num_updates_dev, int bump, void* stream) {
+    if (!table_dev || !ema_table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !ema_args_ok(decay, start, num_updates_dev))
+        return XMC_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ema_table_dev, reinterpret_cast<const int2*>(chunks_dev),
+                       lr, beta1, beta2, eps, grad_scale, (const float*)nullptr, (const int*)nullptr, decay, start,
+                       (const int*)num_updates_dev);
+    hipLaunchKernelGGL(ema_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)nullptr,
+                       (int*)num_updates_dev, bump);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xmc_adam_ema_step_scaled(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
+                                        const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
+                                        float* scale_dev, int32_t* flags_dev, int mode, float growth, float backoff, int interval,
+                                        float decay, int start, int32_t* num_updates_dev, int bump, void* stream) {
+    if (!table_dev || !ema_table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !scale_dev || !flags_dev || interval < 1 ||
+        (mode & 7) == 0 || !ema_args_ok(decay, start, num_updates_dev))
+        return XMC_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int2* ch = reinterpret_cast<const int2*>(chunks_dev);
+    if (mode & XMC_ADAM_CHECK) hipLaunchKernelGGL(adam_check_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ch, flags_dev);
+    if (mode & XMC_ADAM_UPDATE) {
+        hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ema_table_dev, ch, lr, beta1, beta2, eps, 1.f,
+                           (const float*)scale_dev, (const int*)flags_dev, decay, start, (const int*)num_updates_dev);
+        hipLaunchKernelGGL(ema_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)flags_dev,
+                           (int*)num_updates_dev, bump);
     }
     if (mode & XMC_ADAM_RESCALE) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, scale_dev, flags_dev, growth, backoff, interval);
     XMC_LAUNCH_CHECK();

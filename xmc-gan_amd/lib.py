@@ -51,6 +51,10 @@ class AdamEntry(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("m", vp), ("v", vp), ("step", vp), ("n", i64)]
 
 
+class EmaEntry(C.Structure):
+    _fields_ = [("shadow", vp), ("param", vp), ("n", i64)]
+
+
 # name -> argtypes  (restype is int unless listed in _RESTYPE)
 _SIGS = {
     "xmc_abi_version": [],
@@ -148,6 +152,9 @@ _SIGS = {
     "xmc_adam_chunk_elems": [],
     "xmc_adam_step": [vp, i32, vp, i32, f32, f32, f32, f32, f32, vp],
     "xmc_adam_step_scaled": [vp, i32, vp, i32, f32, f32, f32, f32, vp, vp, i32, f32, f32, i32, vp],
+    "xmc_ema_step": [vp, i32, vp, i32, f32, i32, vp, vp, i32, vp],
+    "xmc_adam_ema_step": [vp, vp, i32, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp, i32, vp],
+    "xmc_adam_ema_step_scaled": [vp, vp, i32, vp, i32, f32, f32, f32, f32, vp, vp, i32, f32, f32, i32, f32, i32, vp, i32, vp],
     "xmc_dstem_compose": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "xmc_dstem_compose_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "xmc_dstem_pack": [vp, vp, vp],

@@ -114,12 +114,17 @@ class HipAdam(torch.optim.Optimizer):
         return self._tables[key][:4]
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0, scaler=None):
+    def step(self, closure=None, grad_scale=1.0, scaler=None, ema=None):
         """``grad_scale``: factor applied to every gradient element as the kernel reads it; 1.0 is torch.optim.Adam exactly.
         ``scaler`` (an `ops.LossScaler`, the IEEE-half mode): the gradients are those of scale x loss -- they are read times
         1 / scale; if ANY of them (over all parameter groups) is inf / NaN the step is skipped on the device (no parameter,
-        moment or step counter changes) and the scale backs off; the scaler's counters say so afterwards."""
+        moment or step counter changes) and the scale backs off; the scaler's counters say so afterwards.
+        ``ema`` (a `ParamEMA`): its shadow weights take one update from the weights this step leaves -- inside the Adam kernel
+        for the tensors that have a gradient, in a launch of their own for the shadow tensors that have none -- and its update
+        counter advances by one; a step the scaler skips leaves the shadow and the counter alone as well."""
         assert closure is None
+        if ema is not None:
+            return self._step_ema(grad_scale, scaler, ema)
         groups = []
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
@@ -146,9 +151,189 @@ class HipAdam(torch.optim.Optimizer):
                     L.call("xmc_adam_step_scaled", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
                            float(group["lr"]), float(b1), float(b2), float(group["eps"]), C.c_void_p(scaler.sf.data_ptr()),
                            C.c_void_p(scaler.si.data_ptr()), m, scaler.growth, scaler.backoff, scaler.interval, st)
+        self._repack()
+
+    def _repack(self):
         # the kernels wrote the parameters behind autograd's back: invalidate their packed copies and re-pack, in one launch,
         # the ones that exist (ops._PackEntry)
         changed = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
         for p in changed:
             p._xmc_epoch = getattr(p, "_xmc_epoch", 0) + 1
         ops.repack_params(changed)
+
+    def _step_ema(self, grad_scale, scaler, ema):
+        """`step` with the shadow update of ``ema``: the same launches with `xmc_adam_ema_step[_scaled]` in the place of
+        `xmc_adam_step[_scaled]`, plus one `xmc_ema_step` for the shadow tensors whose parameter has no gradient."""
+        groups, fused = [], set()
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            if not ps[0].is_cuda:
+                raise RuntimeError("HipAdam runs on the GPU only (no CPU fallback)")
+            groups.append((group, self._table(ps, ps[0].device), ema._table(ps, fused=True)))
+            fused.update(id(p) for p in ps)
+        rest = [p for p in ema.params if id(p) not in fused]
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nupd = C.c_void_p(ema.num_updates.data_ptr())
+        decay, start = float(ema.decay), int(ema.start)
+        flag = C.c_void_p(scaler.si.data_ptr()) if scaler is not None else None
+        CHECK, UPDATE, RESCALE = 1, 2, 4
+        one_call = len(groups) == 1 and not rest       # check, update and rescale in one call, as without a shadow set
+        if scaler is not None:
+            assert grad_scale == 1.0
+        if scaler is not None and not one_call:
+            # every group is checked before any tensor (or shadow) is updated; the last update also ends the scaler's step
+            for group, (tab, ch, nt, nc), _ in groups:
+                b1, b2 = group["betas"]
+                L.call("xmc_adam_step_scaled", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
+                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), C.c_void_p(scaler.sf.data_ptr()),
+                       flag, CHECK, scaler.growth, scaler.backoff, scaler.interval, st)
+        if rest:        # (reads the found-inf flag, so before the launch that clears it; bumps the counter only if it is the last launch)
+            etab, ech, ent, enc = ema._table(rest)
+            L.call("xmc_ema_step", C.c_void_p(etab.data_ptr()), ent, C.c_void_p(ech.data_ptr()), enc, decay, start, nupd, flag,
+                   0 if groups else 1, st)
+        for gi, (group, (tab, ch, nt, nc), (etab, _, _, _)) in enumerate(groups):
+            b1, b2 = group["betas"]
+            last = gi == len(groups) - 1
+            if scaler is None:
+                L.call("xmc_adam_ema_step", C.c_void_p(tab.data_ptr()), C.c_void_p(etab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
+                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(grad_scale), decay, start, nupd,
+                       1 if last else 0, st)
+            else:
+                L.call("xmc_adam_ema_step_scaled", C.c_void_p(tab.data_ptr()), C.c_void_p(etab.data_ptr()), nt,
+                       C.c_void_p(ch.data_ptr()), nc, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                       C.c_void_p(scaler.sf.data_ptr()), flag, (CHECK if one_call else 0) | UPDATE | (RESCALE if last else 0), scaler.growth, scaler.backoff,
+                       scaler.interval, decay, start, nupd, 1 if last else 0, st)
+        self._repack()
+
+
+class ParamEMA:
+    """Exponential moving average of a module's parameters, kept on the device (the weights a GAN is sampled from at evaluation
+    time): per applied optimizer step ``e += (1 - d) * (p - e)`` with ``d = 0`` for the first ``start`` updates (the shadow is
+    then a bit-exact copy of the weights) and ``d = decay`` afterwards.  The update count is a device counter and the warm-up is
+    decided in the kernel, so the update replays inside a captured iteration across ``start`` and is skipped together with an
+    optimizer step that the IEEE-half mode's loss scaler skips.
+
+    The shadow tensors are plain f32 device tensors, not the parameters of a module: the kernels write them behind autograd's
+    back, and a module running on them would need the packed-weight bookkeeping of a second network.  To USE the average,
+    `copy_to` a module of the same class: an ordinary, autograd-visible write that invalidates that module's packed weights by
+    the mechanism every ``p.copy_`` uses.  Buffers (BatchNorm running statistics) are not averaged; `copy_to` copies the source
+    module's.  Updated by ``HipAdam.step(ema=...)`` (fused into the Adam kernel) or, after any other optimizer, by `update`."""
+
+    def __init__(self, module, decay, start=0):
+        decay, start = float(decay), int(start)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"ParamEMA: decay must be in [0, 1), got {decay}")
+        if start < 0:
+            raise ValueError(f"ParamEMA: start must be >= 0, got {start}")
+        self.decay, self.start = decay, start
+        self.source = module
+        self.names, self.params = [], []
+        for name, p in module.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"ParamEMA needs contiguous f32 parameters ({name})")
+            self.names.append(name)
+            self.params.append(p)
+        if not self.params:
+            raise ValueError("ParamEMA: the module has no parameters")
+        self.shadow = [p.detach().clone(memory_format=torch.contiguous_format) for p in self.params]
+        self._shadow_of = {id(p): e for p, e in zip(self.params, self.shadow)}
+        device = self.params[0].device
+        self.num_updates = torch.zeros(1, dtype=torch.int32, device=device)
+        self._tables = {}                  # (param ptrs, with_params) -> (table, chunks, ntensors, nchunks, pinned staging...)
+        self._chunk = None
+        self._arenas, self._arena_off = [], 0
+        if device.type == "cuda":
+            self._pinned(0)                # the staging arena exists before anything is captured
+
+    # pinned staging of the device tables, as HipAdam's: only ever added to, and only outside capture
+    def _pinned(self, nbytes):
+        if not self._arenas or self._arena_off + nbytes > self._arenas[-1].numel():
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ParamEMA: pinned staging arena exhausted during graph capture; run a warm-up step first")
+            total = sum(p.numel() for p in self.params)
+            per_table = 32 * len(self.params) + 8 * (total // 4096 + len(self.params)) + 256
+            self._arenas.append(torch.empty(max(8 * per_table, nbytes), dtype=torch.uint8).pin_memory())
+            self._arena_off = 0
+        out = self._arenas[-1][self._arena_off: self._arena_off + nbytes]
+        self._arena_off += nbytes
+        return out
+
+    def _table(self, ps, fused=False):
+        """device table of XmcEmaEntry for the parameters ``ps`` (in that order; a parameter that is not tracked gets a NULL
+        shadow), uploaded from pinned staging.  ``fused``: the table rides beside HipAdam's own (same tensors, same order, its chunk
+        list); otherwise it comes with the chunk list of a standalone launch over exactly these tensors, all of them tracked."""
+        with_params = not fused
+        key = (tuple(p.data_ptr() for p in ps), with_params)
+        hit = self._tables.get(key)
+        if hit is not None:
+            return hit[:4]
+        device = ps[0].device
+        if device.type != "cuda":
+            raise RuntimeError("ParamEMA runs on the GPU only (no CPU fallback)")
+        if self._chunk is None:
+            self._chunk = L.load().xmc_adam_chunk_elems()
+        ents = (L.EmaEntry * len(ps))()
+        chunks = []
+        for i, p in enumerate(ps):
+            e = self._shadow_of.get(id(p))
+            if e is None and with_params:
+                raise RuntimeError("ParamEMA: not a parameter of the averaged module")
+            ents[i].shadow, ents[i].param, ents[i].n = (e.data_ptr() if e is not None else None), p.data_ptr(), p.numel()
+            chunks += [(i, c) for c in range((p.numel() + self._chunk - 1) // self._chunk)]
+        raw = bytes(ents)
+        chb = torch.tensor(chunks, dtype=torch.int32).numpy().tobytes() if with_params else b""
+        n0, n1 = (len(raw) + 63) // 64 * 64, (len(chb) + 63) // 64 * 64
+        tab_h, ch_h = self._pinned(n0), self._pinned(n1)
+        tab_h[: len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        tab = tab_h.to(device, non_blocking=True)
+        ch = None
+        if with_params:
+            ch_h[: len(chb)].copy_(torch.frombuffer(bytearray(chb), dtype=torch.uint8))
+            ch = ch_h.to(device, non_blocking=True).view(torch.int32)
+        self._tables[key] = (tab, ch, len(ps), len(chunks), tab_h, ch_h)
+        return self._tables[key][:4]
+
+    @torch.no_grad()
+    def update(self, skip_flag=None):
+        """one update of every shadow tensor from the current weights, in one launch, and the counter's bump.  ``skip_flag``: a
+        device int32 (a loss scaler's found-inf flag); while it is non-zero the launch changes nothing."""
+        tab, ch, nt, nc = self._table(self.params)
+        L.call("xmc_ema_step", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc, float(self.decay), int(self.start),
+               C.c_void_p(self.num_updates.data_ptr()), C.c_void_p(skip_flag.data_ptr()) if skip_flag is not None else None, 1,
+               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def state_dict(self):
+        """``{"shadow": {parameter name: tensor}, "num_updates", "decay", "start"}`` (reads the counter back: synchronises)"""
+        return {"shadow": {n: e.detach().clone() for n, e in zip(self.names, self.shadow)},
+                "num_updates": int(self.num_updates.item()), "decay": self.decay, "start": self.start}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """``sd["shadow"]`` may be any mapping that holds the parameters' names (a generator's plain ``state_dict`` does)"""
+        missing = [n for n in self.names if n not in sd["shadow"]]
+        if missing:
+            raise KeyError(f"ParamEMA.load_state_dict: no shadow for {missing}")
+        for n, e in zip(self.names, self.shadow):
+            e.copy_(sd["shadow"][n])             # in place: the device tables hold these addresses
+        self.num_updates.fill_(int(sd["num_updates"]))
+        if "decay" in sd:
+            self.decay = float(sd["decay"])
+        if "start" in sd:
+            self.start = int(sd["start"])
+
+    @torch.no_grad()
+    def copy_to(self, module):
+        """write the shadow weights, and the source module's buffers, into ``module`` (same class as the source): ``p.copy_`` on the
+        parameters themselves, which autograd sees (``p._version`` moves), so cached packed copies of them are stale by
+        construction.  Returns ``module``."""
+        targets = dict(module.named_parameters())
+        if set(targets) != set(self.names):
+            raise KeyError("ParamEMA.copy_to: the module's parameters are not those of the averaged module")
+        for n, e in zip(self.names, self.shadow):
+            targets[n].copy_(e)
+        src = dict(self.source.named_buffers())
+        for n, b in module.named_buffers():
+            b.copy_(src[n])
+        return module

@@ -38,7 +38,7 @@ from xmc_gan.utils.logger import setup_logger
 from xmc_gan.utils.miscc import count_params
 from xmc_gan.utils.visual import ScalarLog, fid_between, flush_saves, save_image, save_image_async, to_uint8_hwc
 from xmc_gan_amd import ops, parallel
-from xmc_gan_amd.optim import HipAdam
+from xmc_gan_amd.optim import HipAdam, ParamEMA
 
 _GEN_ARCH = {"DF_GEN": DF_GEN, "CONCEPT_IN_DF_GEN": CONCEPT_IN_DF_GEN, "CONCEPT_OUT_DF_GEN": CONCEPT_OUT_DF_GEN,
              # word-attention generators of model/concept_gan.py; upstream keeps these two names commented out (train_gan.py:44)
@@ -72,6 +72,11 @@ def parse_args(argv=None):
     parser.add_argument('--log_each_step', type=int, default=0,
                         help="1: the reference's loss line after EVERY generator step (one host synchronisation per iteration); default: "
                              'at the first step and every LOG_INTERVAL steps')
+    parser.add_argument('--ema_decay', type=float, default=0.0,
+                        help='> 0: keep an exponential moving average of the generator weights on the device (typical: 0.999 / 0.9999); '
+                             'the per-epoch sample grid, eval() and netG_ema_<epoch>.pth use it.  0 (default): off')
+    parser.add_argument('--ema_start', type=int, default=0,
+                        help='generator steps before the averaging starts: until then the average is a copy of the weights')
     return parser.parse_args(argv)
 
 
@@ -126,16 +131,26 @@ def img_loss(real_imgs, fake_imgs, labels, b_global):
 class StepOptions:
     """Engine-side switches of an iteration (not part of the reference cfg)."""
 
-    def __init__(self, gather_negatives=False, graph=False, log_each_step=True):
+    def __init__(self, gather_negatives=False, graph=False, log_each_step=True, ema=None):
         self.gather_negatives = gather_negatives
+        self.ema = ema                        # xmc_gan_amd.optim.ParamEMA of the generator: one update per applied generator step
         self.graph = graph                    # train(): replay the iteration as hipGraphs (xmc_gan_amd.graph.GraphedIteration)
         self.log_each_step = log_each_step    # train(): read the four logged losses back after every generator step
 
 
-def _step(optimizer, scaler):
+def _step(optimizer, scaler, ema=None):
     """optimizer.step(), with the dynamic loss scale only where there is one (IEEE-half mode): any torch.optim optimizer works
-    in the bf16 / fp32 modes, as upstream's torch.optim.Adam does"""
-    return optimizer.step(scaler=scaler) if scaler is not None else optimizer.step()
+    in the bf16 / fp32 modes, as upstream's torch.optim.Adam does.  ``ema``: the weight average takes this step's weights -- inside
+    HipAdam's kernel, or in a launch of its own after any other optimizer"""
+    if ema is None:
+        return optimizer.step(scaler=scaler) if scaler is not None else optimizer.step()
+    if isinstance(optimizer, HipAdam):
+        return optimizer.step(scaler=scaler, ema=ema)
+    if scaler is not None:
+        raise RuntimeError('a weight average under the dynamic loss scale needs HipAdam (the skipped steps are known on the device only)')
+    out = optimizer.step()
+    ema.update()
+    return out
 
 
 def _set_requires_grad(module, flag):
@@ -322,7 +337,7 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
         finally:
             _set_requires_grad(netD, True)
         parallel.allreduce_mean_grads(netG.parameters())
-        _step(optimizerG, sc_g)
+        _step(optimizerG, sc_g, opts.ema)
         it_state['i'] = 0
         out.update(errG=errG.detach(), errG_fake=errG_fake.detach())
     out['fake'] = fake.detach()
@@ -460,9 +475,15 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
     ``opts.graph`` (the entry point's default, ``--graph 1``): the loop body runs as hipGraph replays
     (xmc_gan_amd.graph.GraphedIteration: two eager warm-up iterations, one capture per N_CRITIC phase, collectives as eager
     seams between graph segments); a batch is copied into the graph's static inputs and the losses stay on the device until they
-    are logged -- at the first step and every LOG_INTERVAL steps unless ``opts.log_each_step``."""
+    are logged -- at the first step and every LOG_INTERVAL steps unless ``opts.log_each_step``.
+
+    ``opts.ema`` (a `ParamEMA` of ``netG``, ``--ema_decay``): the per-epoch grid and `eval` sample from the averaged weights,
+    written into a second, eval-mode generator that exists for nothing else (the captured iteration never sees it); checkpoints
+    add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training."""
     device = next(netG.parameters()).device
     opts = opts or StepOptions()
+    ema = opts.ema
+    netG_ema = type(netG)(cfg).to(device).eval().requires_grad_(False) if ema is not None else None
     it_state, last, nsteps = {}, {}, 0
     fixed = None
     visual = img_dir is not None and parallel.rank() == 0
@@ -548,10 +569,13 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
             logger.info('loss scale ' + ' '.join(f"{k}: {v['scale']:g} ({v['skipped_steps']} skipped)" for k, v in sc_stats.items()))
             if all(v['scale'] <= 1.0 and v['last_step_skipped'] for v in sc_stats.values()):
                 raise FloatingPointError('every backward of the f16 mode overflows at loss scale 1: the run has diverged')
+        if ema is not None and parallel.rank() == 0:
+            ema.copy_to(netG_ema)                # this epoch's averaged generator (grid, checkpoint, eval)
         if visual and fixed is not None:
             with torch.no_grad():
-                netG.eval()
-                fake = netG(noise=fixed['noise'], sent_embs=fixed['sent'], words_embs=fixed['words'], mask=fixed['mask'])
+                gen = netG_ema if ema is not None else netG
+                gen.eval()
+                fake = gen(noise=fixed['noise'], sent_embs=fixed['sent'], words_embs=fixed['words'], mask=fixed['mask'])
                 save_image_async(fake, f'{img_dir}/fake_samples_epoch_{epoch:03d}.png', normalize=True, scale_each=True)
         if epoch > 50 and parallel.rank() == 0:
             torch.save(netG.state_dict(), f'{model_dir}/netG_{epoch:03d}.pth')
@@ -560,9 +584,13 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
             torch.save(optimizerD.state_dict(), f'{model_dir}/optimizerD.pth')
             if ops.loss_scaler_state():          # IEEE-half mode: the dynamic loss scales are optimizer state too
                 torch.save(ops.loss_scaler_state(), f'{model_dir}/loss_scale.pth')
+            if ema is not None:                  # the averaged generator, loadable wherever netG_<epoch>.pth is, and the average's counter
+                torch.save(netG_ema.state_dict(), f'{model_dir}/netG_ema_{epoch:03d}.pth')
+                torch.save(dict(num_updates=int(ema.num_updates.item()), decay=ema.decay, start=ema.start), f'{model_dir}/ema_state.pth')
             logger.info('Save models')
             if test_loader is not None:
-                eval(loader=test_loader, state_epoch=epoch, text_encoder=text_encoder, netG=netG, logger=logger, num_samples=6000,
+                eval(loader=test_loader, state_epoch=epoch, text_encoder=text_encoder, netG=netG_ema if ema is not None else netG,
+                     logger=logger, num_samples=6000,
                      save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None, writer=writer)
     flush_saves()                    # the sample grids queued for the writer thread are on disk when train() returns
     last = _detached(last)
@@ -634,6 +662,8 @@ def build_models(device):
 
 def main(argv=None):
     args = parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0 or args.ema_start < 0:
+        raise SystemExit('--ema_decay must be in [0, 1) and --ema_start >= 0')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -724,16 +754,33 @@ def main(argv=None):
     elif cfg.DISC.ENCODER_DIR:
         netD.load_state_dict(torch.load(f'{PROJ_DIR}/{cfg.DISC.ENCODER_DIR}', map_location=device), strict=False)
 
+    # the generator's weight average (--ema_decay > 0): after the broadcast / the resume, so that it starts from the weights in use
+    ema = None
+    if args.ema_decay > 0:
+        ema = ParamEMA(netG, args.ema_decay, args.ema_start)
+        logger.info(f'generator weight EMA: decay {ema.decay}, averaging after {ema.start} generator steps')
+        if state_epoch != 0:
+            f_w, f_s = f'{model_dir}/netG_ema_{state_epoch:03d}.pth', f'{model_dir}/ema_state.pth'
+            if os.path.isfile(f_w) and os.path.isfile(f_s):
+                saved = torch.load(f_s, map_location='cpu')
+                ema.load_state_dict(dict(shadow=torch.load(f_w, map_location=device), num_updates=saved['num_updates']))
+                logger.info(f'Load EMA generator, epoch : {state_epoch} ({saved["num_updates"]} updates; saved with decay '
+                            f'{saved["decay"]}, start {saved["start"]})')
+            else:
+                logger.info(f'no netG_ema_{state_epoch:03d}.pth / ema_state.pth in {model_dir}: the EMA starts from netG_{state_epoch:03d}.pth')
+
     writer = ScalarLog(log_dir, args.log_type, run_name=cfg.CONFIG_NAME) if rank == 0 else None
     last = train(train_loader=train_loader, test_loader=test_loader, state_epoch=state_epoch, text_encoder=text_encoder,
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
-                 opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step)),
+                 opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
+                                  ema=ema),
                  img_dir=img_dir if rank == 0 else None, writer=writer)
     if writer is not None:
         writer.close()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.destroy_process_group()
+    main.last_ema = ema                      # (None without --ema_decay)
     main.last_models = (netG, netD)          # (for callers that drive main() in-process: the tests compare runs by their final weights)
     return last
 
