@@ -319,6 +319,71 @@ def test_product_never_touches_the_oracle_or_a_cpu_fallback():
     assert "/root/reference" not in bench                                  # nothing at run time reads the reference
 
 
+OPS_LAYERS = ("_config", "_engine", "_nodes_leaf", "_nodes_conv", "_nodes_block", "_nodes_loss", "_functional")
+
+
+def test_ops_modules_import_only_from_earlier_layers():
+    """xmc_gan_amd.ops is layered: a module imports only from the modules before it in OPS_LAYERS, nothing binds a name in another
+    module after the fact, and every name a module reads is a builtin or bound somewhere in that module (a flat walk: one set of
+    bound names per file, which is what catches a name that only a later `setattr` from outside would have supplied)."""
+    import ast
+    import builtins
+    pkg = os.path.join(ROOT, "xmc-gan_amd", "ops")
+    files = sorted(f[:-3] for f in os.listdir(pkg) if f.endswith(".py"))
+    assert files == sorted(OPS_LAYERS + ("__init__",))
+    for mod in files:
+        tree = ast.parse(open(os.path.join(pkg, mod + ".py")).read())
+        earlier = OPS_LAYERS if mod == "__init__" else OPS_LAYERS[:OPS_LAYERS.index(mod)]
+        bound, loaded = set(dir(builtins)), []
+        for n in ast.walk(tree):
+            if isinstance(n, ast.ImportFrom) and n.level == 1:          # from ._x import a / from . import _x
+                targets = [n.module] if n.module else [a.name for a in n.names]
+                assert all(t in earlier for t in targets), f"ops/{mod}.py imports {targets}: not an earlier layer"
+            if isinstance(n, (ast.Import, ast.ImportFrom)):
+                bound.update((a.asname or a.name).split(".")[0] for a in n.names)
+            elif isinstance(n, (ast.FunctionDef, ast.ClassDef)):
+                bound.add(n.name)
+            elif isinstance(n, ast.arg):
+                bound.add(n.arg)
+            elif isinstance(n, ast.Global):
+                bound.update(n.names)
+            elif isinstance(n, ast.ExceptHandler) and n.name:
+                bound.add(n.name)
+            elif isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load):
+                loaded.append(n)
+            elif isinstance(n, ast.Name):                                # assignment, for / with / comprehension targets
+                bound.add(n.id)
+        undefined = sorted({f"{n.id} (line {n.lineno})" for n in loaded if n.id not in bound})
+        assert not undefined, f"ops/{mod}.py reads names it never binds: {undefined}"
+    assert "setattr(" not in open(os.path.join(pkg, "__init__.py")).read()
+
+
+def test_ops_package_reexports_the_defining_objects():
+    """`ops.<name>` is the object its module defines, for every function and class of every layer; the package exports no module
+    object besides its layers and no copy of the precision mode (`precision()` reads the live one)."""
+    import importlib
+    import types
+    from xmc_gan_amd import ops
+    layers = [importlib.import_module("xmc_gan_amd.ops." + m) for m in OPS_LAYERS]
+    seen = 0
+    for m in layers:
+        for name, obj in vars(m).items():
+            if isinstance(obj, (type, types.FunctionType)) and obj.__module__ == m.__name__:
+                assert getattr(ops, name) is obj, (m.__name__, name)
+                seen += 1
+    assert seen > 150
+    stray = [k for k, v in vars(ops).items() if isinstance(v, types.ModuleType) and v not in layers]
+    assert not stray, stray
+    assert not hasattr(ops, "_PRECISION")
+    assert ops._pack_cache is layers[1]._pack_cache and ops._pooled_grads is layers[1]._pooled_grads and ops._arena is layers[1]._arena
+    try:
+        ops.set_precision("fp32")            # (selects a library build by name; nothing is loaded, so it runs without a GPU)
+        assert ops.precision() == "fp32" and ops.act_dtype() == torch.float32
+    finally:
+        ops.set_precision("bf16")
+    assert ops.precision() == "bf16"
+
+
 def test_cli_flags_match_reference():
     import xmc_gan.train_gan as tg
     a = tg.parse_args([])

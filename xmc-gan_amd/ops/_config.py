@@ -1,13 +1,10 @@
-"""xmc_gan_amd.ops: configuration of the engine: precision modes and loss scales, dispatch switches, thread-local contexts, small helpers.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
+"""xmc_gan_amd.ops, layer 1: configuration of the engine: precision modes and loss scales, dispatch switches, thread-local contexts,
+small helpers.  Imports no other module of the package."""
 import ctypes as C
 import os
 import threading
-import weakref
-import numpy as np
 import torch
 from .. import lib as L
-from .. import prof
 
 
 # ------------------------------------------------------------------------------------------ config
@@ -15,27 +12,26 @@ _state = threading.local()
 # kernel / operator A/B switches (comma-separated tokens; unset in production).  The C dispatchers read the same variable
 # (common.h: xmc_debug_off); the one host-side token is "no_fused_blocks" (blocks composed from the fine-grained Functions).
 _DEBUG_DISPATCH = frozenset(t for t in os.environ.get("XMC_DEBUG_DISPATCH", "").split(",") if t)
-_PRECISION = os.environ.get("XMC_PRECISION", "bf16")
+_precision = [os.environ.get("XMC_PRECISION", "bf16")]          # read through `precision()`
 
 
 def set_precision(p):
     """'bf16' (default: bf16 activations / MFMA operands, f32 accumulate, f32 parameters), 'f16' (IEEE half in the same places,
     through the f16 build of the library: same MFMA rate, 11 significant bits instead of 8 -- the mode whose losses stay within
     1e-3 of the f32 reference -- with the backward passes run on LOSS_SCALE x the loss, see `loss_scale`) or 'fp32'."""
-    global _PRECISION
     assert p in ("bf16", "f16", "fp32")
-    _PRECISION = p
+    _precision[0] = p
     reset_loss_scalers()
     L.use_variant("f16" if p == "f16" else "bf16")
     bump_weights_epoch()           # packed weights of the other format / library are not ours
 
 
 def precision():
-    return _PRECISION
+    return _precision[0]
 
 
 def act_dtype():
-    return {"bf16": torch.bfloat16, "f16": torch.float16, "fp32": torch.float32}[_PRECISION]
+    return {"bf16": torch.bfloat16, "f16": torch.float16, "fp32": torch.float32}[precision()]
 
 
 _PRECISE = [None]           # None: on in the IEEE-half mode (the mode that promises 1e-3), off in bf16
@@ -49,9 +45,9 @@ def precise_trunk(on="query"):
     if on != "query":
         _PRECISE[0] = None if on is None else bool(on)
         return
-    if "no_precise" in _DEBUG_DISPATCH or _PRECISION == "fp32":
+    if "no_precise" in _DEBUG_DISPATCH or precision() == "fp32":
         return False
-    return _PRECISION == "f16" if _PRECISE[0] is None else _PRECISE[0]
+    return precision() == "f16" if _PRECISE[0] is None else _PRECISE[0]
 
 
 # f16 activation gradients: a hinge / InfoNCE gradient of 1/B spread over a 256x256x32 map is ~1e-6 per element, far into
@@ -97,7 +93,7 @@ _scalers = {}
 def loss_scaler(phase, device):
     """the `LossScaler` of a backward phase ("D", "GP", "G") in the IEEE-half mode, None in the other modes.  Created on first use
     (outside graph capture: the warm-up iterations come first) and kept across iterations."""
-    if _PRECISION != "f16":
+    if precision() != "f16":
         return None
     key = (phase, torch.device(device).index)
     sc = _scalers.get(key)
@@ -123,7 +119,7 @@ def loss_scaler_state():
 
 def load_loss_scaler_state(state, device):
     """restore `loss_scaler_state()` (a resumed IEEE-half run continues at its scale instead of re-learning it from 4096)"""
-    if _PRECISION != "f16":
+    if precision() != "f16":
         return
     for ph, (scale, good, skipped) in state.items():
         sc = _scalers[(ph, torch.device(device).index)] = LossScaler(device, init=float(scale))
@@ -131,13 +127,13 @@ def load_loss_scaler_state(state, device):
 
 
 def gp_inner_scale():
-    return GP_INNER_SCALE_F16 if _PRECISION == "f16" else 1.0
+    return GP_INNER_SCALE_F16 if precision() == "f16" else 1.0
 
 
 def loss_scale(phase="step"):
     """INITIAL factor of the D / G backward passes (the running value lives in `loss_scaler(phase)`); the rounding oracle of the
     tests rounds gradient tensors at this scale."""
-    return LOSS_SCALE_F16 if _PRECISION == "f16" else 1.0
+    return LOSS_SCALE_F16 if precision() == "f16" else 1.0
 
 
 class composable:
@@ -150,6 +146,26 @@ class composable:
 
     def __exit__(self, *a):
         _state.composable = self.prev
+
+
+def debug_switch(token):
+    """True when `token` is listed in XMC_DEBUG_DISPATCH (A/B experiments; unset in production)"""
+    return token in _DEBUG_DISPATCH
+
+
+class fixed_order:
+    """Context manager: the reductions that feed activations (GroupNorm statistics, the attention query gradient) in a fixed summation
+    order (xmc_set_fixed_order: one workgroup per reduction target).  A test mode -- it costs those launches their parallelism -- that
+    makes an iteration of the attention-modulation generators repeatable, so that their gradient tests need not budget for run-to-run
+    spread."""
+
+    def __enter__(self):
+        self.was = L.load().xmc_set_fixed_order(1)
+        return self
+
+    def __exit__(self, *a):
+        L.load().xmc_set_fixed_order(self.was)
+        return False
 
 
 def fused_blocks():
@@ -247,3 +263,7 @@ _weights_epoch = [0]
 def bump_weights_epoch():
     """Invalidate EVERY cached packed weight (parameters replaced wholesale behind autograd's back)."""
     _weights_epoch[0] += 1
+
+
+if precision() != "bf16":          # XMC_PRECISION in the environment: select the matching build of the library
+    set_precision(precision())

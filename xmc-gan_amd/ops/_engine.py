@@ -1,10 +1,8 @@
-"""xmc_gan_amd.ops: layer geometry, packed-weight cache, the raw convolution launches (forward, data gradient, weight gradient, composed stem) and the zero-filled scratch pools.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
+"""xmc_gan_amd.ops, layer 2: the raw launches.  Layer geometry, the packed-weight cache, the zero-filled scratch pools and every
+launch that more than one node module needs (convolution forward / data gradient / weight gradient, composed stem, cast, affine
+modulation, block sum backward) as plain functions on tensors: no autograd node lives here.  Imports `_config` only."""
 import ctypes as C
-import os
-import threading
 import weakref
-import numpy as np
 import torch
 from .. import lib as L
 from .. import prof
@@ -202,6 +200,16 @@ def repack_params(params):
     return len(jobs)
 
 
+def _cast_raw(x, dtype):
+    """x in `dtype`: x itself when it already is, else a contiguous copy (xmc_cast)"""
+    if x.dtype == dtype:
+        return x
+    x = x.contiguous()
+    y = torch.empty_like(x, dtype=dtype)
+    L.call("xmc_cast", _p(x), _p(y), x.numel(), _code(x.dtype), _code(dtype), _st())
+    return y
+
+
 def _upconv_fwd_raw(x, w, bias, geom, act, out_dtype):
     """conv3x3(nearest_up2(x), w) + bias on the LOW-resolution x [N,H,W,Cs] -> [N,2H,2W,Cd]: four output-parity classes,
     each a 2x2-tap convolution with pre-summed weights (4/9 of the MACs, the upsampled tensor never exists)."""
@@ -361,8 +369,8 @@ def _conv1x1_pair_raw(x, w, bias, geom, out_dtype):
             return y
         if rc != 1:
             L.check(rc, "xmc_conv_pw1x1_split")
-    y32 = _conv_fwd_raw(CastFn.apply(x, torch.float32), w, bias, geom, L.ACT_NONE, torch.float32)
-    return CastFn.apply(y32, out_dtype)
+    y32 = _conv_fwd_raw(_cast_raw(x, torch.float32), w, bias, geom, L.ACT_NONE, torch.float32)
+    return _cast_raw(y32, out_dtype)
 
 
 class _StagedMask:
@@ -669,6 +677,53 @@ def _conv_wgrad_raw(x, dy, geom, scale=None, up=False, want_bias=False, bias_dot
     L.call("xmc_unpack_wgrad_grouped", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
            _p(geom.perm_dev(x.device)), 0, geom.groups, _st())
     return gw
+
+
+# ------------------------------------------------------------------------------------------ pointwise passes shared by the node modules
+def _axpby_bwd_fused(dy, b, alpha, up, ymask=None, want_db=True):
+    """(da, db, dalpha) of a + alpha*b / up2(a) + alpha*b from one pass over dy and b (not differentiable again).
+    ``ymask``: the forward applied LeakyReLU to the sum; dy is multiplied by LeakyReLU'(y) first.  ``want_db`` False: alpha*dy
+    is not written (db is None); the caller hands alpha to the consumers of db instead."""
+    dy = dy.contiguous()
+    N, OH, OW, Cc = dy.shape
+    H, W = (OH // 2, OW // 2) if up else (OH, OW)
+    al = alpha.detach().reshape(-1).float()
+    db = torch.empty_like(dy) if want_db else None
+    da = torch.empty((N, H, W, Cc), dtype=dy.dtype, device=dy.device) if (up or ymask is not None) else None
+    dot = _zeros_f32_out(1, dy.device)
+    L.call("xmc_axpby_bwd", _p(dy), _p(b), _p(al), _p(db), _p(da), _p(dot), N, H, W, Cc, 1 if up else 0, _p(ymask), _code(dy.dtype), _st())
+    return da, db, dot.reshape(alpha.shape).to(alpha.dtype)
+
+
+def _affine_fwd_raw(x, ps, slope):
+    """ps: (g0, b0) or (g0, b0, g1, b1), contiguous f32 [N, C]"""
+    N, H, W, Cc = x.shape
+    for t in ps:
+        assert t.shape == (N, Cc), (t.shape, (N, Cc))
+    y = torch.empty_like(x)
+    ptrs = [_p(t) for t in ps] + ([] if len(ps) == 4 else [None, None])
+    L.call("xmc_affine2_act_fwd", _p(x), *ptrs, _p(y), N, H * W, Cc, float(slope), _code(x.dtype), _st())
+    return y
+
+
+def _affine_bwd_raw(x, dy, ps, slope, dx_acc=None, alpha=None, dot=None, want_sumpool=False):
+    """-> dx, red [len(ps), N, C] (the gradients of ps).  ``dx_acc``: another gradient of x, added on the way out.
+    ``alpha`` / ``dot`` (f32 [1] each): dy is the UNSCALED gradient from a consumer `sum + alpha * f(y)`: dot += <dy, y>, dy *= alpha
+    (xmc_affine2_act_bwd_dot).  ``want_sumpool``: -> dx, red, 2x2 sum pool of dx (same pass)."""
+    N, H, W, Cc = x.shape
+    dx = torch.empty_like(x)
+    if dx_acc is not None:
+        dx_acc = dx_acc.contiguous()
+        assert dx_acc.shape == x.shape and dx_acc.dtype == x.dtype
+    nred = len(ps)
+    red = _zeros_f32((nred, N, Cc), x.device)
+    ptrs = [_p(t) for t in ps] + ([] if nred == 4 else [None, None])
+    rptrs = [_p(red[i]) for i in range(nred)] + ([] if nred == 4 else [None, None])
+    assert (alpha is None) == (dot is None)
+    dxp = torch.empty((N, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device) if want_sumpool else None
+    L.call("xmc_affine2_act_bwd_dot_pool", _p(x), _p(dy), *ptrs, _p(dx), *rptrs, _p(dx_acc), _p(alpha), _p(dot), _p(dxp), N, H, W, Cc,
+           float(slope), _code(x.dtype), _st())
+    return (dx, red, dxp) if want_sumpool else (dx, red)
 
 
 # ------------------------------------------------------------------------------------------ discriminator stem (csrc/dstem.hip)

@@ -1,22 +1,10 @@
-"""xmc_gan_amd.ops: functional wrappers over the nodes.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
-import ctypes as C
-import os
-import threading
-import weakref
-import numpy as np
+"""xmc_gan_amd.ops, layer 7 (the last): one-line functional wrappers over the nodes.  May import every other module of the package."""
 import torch
-from .. import lib as L
-from .. import prof
-from ._config import (
-    _PRECISION, act_dtype, set_precision)
-from ._nodes_conv import (
-    AxpbyUpFn, UpConvFn)
-from ._nodes_block import (
-    Affine2LreluFn, AttnPoolFn, AxpbyFn, CastFn, GapFn, GroupNormFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn,
-    SumPool2Fn, Up2Fn)
-from ._nodes_loss import (
-    ContrastiveFn, HingeFn)
+from ._config import act_dtype
+from ._nodes_leaf import AxpbyFn, AxpbyUpFn, CastFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, SumPool2Fn, Up2Fn
+from ._nodes_conv import UpConvFn
+from ._nodes_block import Affine2LreluFn, AttnPoolFn, GroupNormFn
+from ._nodes_loss import ContrastiveFn, HingeFn
 
 
 # ------------------------------------------------------------------------------------------ functional sugar
@@ -87,7 +75,3 @@ def contrastive(a, b, labels=None, inv_num_pos=None):
 
 def cast(x, dtype):
     return CastFn.apply(x, dtype)
-
-
-if _PRECISION != "bf16":          # XMC_PRECISION in the environment: select the matching build of the library
-    set_precision(_PRECISION)

@@ -1,156 +1,14 @@
-"""xmc_gan_amd.ops: pointwise nodes, the discriminator blocks (first- and second-order), pooling, affine modulation, GroupNorm / BatchNorm, region attention.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
-import ctypes as C
-import os
-import threading
-import weakref
-import numpy as np
+"""xmc_gan_amd.ops, layer 5: the discriminator blocks (first- and second-order) and the nodes of affine modulation, GroupNorm /
+BatchNorm and region attention.  Imports `_config`, `_engine`, `_nodes_leaf` and `_nodes_conv`."""
 import torch
 from .. import lib as L
-from .. import prof
-from ._config import (
-    _DEBUG_DISPATCH, _code, _need_cuda, _p, _second_order, _skip_wgrad, _st, fused_blocks, pad_to, precise_trunk)
+from ._config import _DEBUG_DISPATCH, _code, _need_cuda, _p, _second_order, _skip_wgrad, _st, precise_trunk
 from ._engine import (
-    _StagedMask, _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw, _dstem_border_fwd_raw,
-    _dstem_compose_bwd_raw, _dstem_compose_raw, _dstem_dgrad_raw, _dstem_fwd_raw, _dstem_sc_operands,
+    _StagedMask, _affine_bwd_raw, _affine_fwd_raw, _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw,
+    _dstem_border_fwd_raw, _dstem_compose_bwd_raw, _dstem_compose_raw, _dstem_dgrad_raw, _dstem_fwd_raw, _dstem_sc_operands,
     _dstem_wgrad_raw, _pooled_put, _zeros_f32, _zeros_f32_out)
-from ._nodes_conv import (
-    _axpby_bwd_fused)
-
-
-# ------------------------------------------------------------------------------------------ pointwise
-class CastFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, dtype):
-        ctx.src = x.dtype
-        if x.dtype == dtype:
-            return x
-        x = x.contiguous()
-        y = torch.empty_like(x, dtype=dtype)
-        L.call("xmc_cast", _p(x), _p(y), x.numel(), _code(x.dtype), _code(dtype), _st())
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return CastFn.apply(dy, ctx.src), None
-
-
-class MaskFn(torch.autograd.Function):
-    """ref > 0 ? dy : slope*dy  (derivative of LeakyReLU/ReLU applied to dy; linear in dy)."""
-
-    @staticmethod
-    def forward(ctx, dy, ref, slope):
-        dy = dy.contiguous()
-        if dy.dtype != ref.dtype:
-            dy = dy.to(ref.dtype)
-        out = torch.empty_like(dy)
-        L.call("xmc_lrelu_mask", _p(dy), _p(ref), _p(out), dy.numel(), float(slope), _code(dy.dtype), _st())
-        ctx.slope = slope
-        ctx.save_for_backward(ref)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (ref,) = ctx.saved_tensors
-        return MaskFn.apply(g, ref, ctx.slope), None, None
-
-
-class LreluFn(torch.autograd.Function):
-    """nn.LeakyReLU(0.2) (df_gan.py:85,158,214-222,274,277); slope 0 gives nn.ReLU."""
-
-    @staticmethod
-    def forward(ctx, x, slope):
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        L.call("xmc_lrelu", _p(x), _p(y), x.numel(), float(slope), _code(x.dtype), _st())
-        ctx.slope = slope
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
-        return MaskFn.apply(dy, y, ctx.slope), None
-
-
-class TanhBwdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, dy, y):
-        dy = dy.contiguous()
-        if dy.dtype != y.dtype:
-            dy = dy.to(y.dtype)
-        out = torch.empty_like(dy)
-        L.call("xmc_tanh_bwd", _p(dy), _p(y), _p(out), dy.numel(), _code(dy.dtype), _st())
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        raise NotImplementedError("second derivative through tanh is not on the XMC-GAN path")
-
-
-class ScaleFn(torch.autograd.Function):
-    """alpha * x with alpha a device scalar (f32 tensor with one element)."""
-
-    @staticmethod
-    def forward(ctx, x, alpha):
-        x = x.contiguous()
-        a = alpha.detach().reshape(-1).float()
-        y = torch.empty_like(x)
-        L.call("xmc_scale", _p(x), _p(a), _p(y), x.numel(), _code(x.dtype), _st())
-        ctx.save_for_backward(x, alpha)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, alpha = ctx.saved_tensors
-        dx = ScaleFn.apply(dy, alpha) if ctx.needs_input_grad[0] else None
-        da = DotFn.apply(dy, x).reshape(alpha.shape) if ctx.needs_input_grad[1] else None
-        return dx, da
-
-
-class DotFn(torch.autograd.Function):
-    """sum(a*b) -> f32 [1]."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = a.contiguous(), b.contiguous()
-        if a.dtype != b.dtype:
-            b = b.to(a.dtype)
-        out = _zeros_f32_out(1, a.device)
-        L.call("xmc_dot", _p(a), _p(b), _p(out), a.numel(), _code(a.dtype), _st())
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        da = ScaleFn.apply(b, g) if ctx.needs_input_grad[0] else None
-        db = ScaleFn.apply(a, g) if ctx.needs_input_grad[1] else None
-        return da, db
-
-
-class AxpbyFn(torch.autograd.Function):
-    """a + alpha*b  (shortcut + gamma*residual, df_gan.py:200,284)."""
-
-    @staticmethod
-    def forward(ctx, a, b, alpha):
-        a, b = a.contiguous(), b.contiguous()
-        al = alpha.detach().reshape(-1).float()
-        y = torch.empty_like(a)
-        L.call("xmc_axpby", _p(a), _p(b), _p(al), _p(y), a.numel(), _code(a.dtype), _st())
-        ctx.save_for_backward(b, alpha)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        b, alpha = ctx.saved_tensors
-        if not torch.is_grad_enabled() and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and fused_blocks():
-            _, db, dal = _axpby_bwd_fused(dy, b, alpha, up=False)
-            return (dy if ctx.needs_input_grad[0] else None), db, dal
-        da = dy if ctx.needs_input_grad[0] else None
-        db = ScaleFn.apply(dy, alpha) if ctx.needs_input_grad[1] else None
-        dal = DotFn.apply(dy, b).reshape(alpha.shape) if ctx.needs_input_grad[2] else None
-        return da, db, dal
+from ._nodes_leaf import CastFn
+from ._nodes_conv import _bias_padded
 
 
 class ResDFn(torch.autograd.Function):
@@ -179,13 +37,7 @@ class ResDFn(torch.autograd.Function):
         else:
             xp = torch.empty((N, H // 2, W // 2, x.shape[3]), dtype=dt, device=x.device)
             L.call("xmc_sumpool2", _p(x), _p(xp), N, H, W, x.shape[3], 0.25, _code(dt), _st())
-        bp = None
-        if ws is not None and bs is not None:
-            bp = bs.detach().float()
-            cd_p = pad_to(gs.cout, 8)
-            if bp.numel() < cd_p:
-                bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
-            bp = bp.contiguous()
+        bp = _bias_padded(bs, gs) if ws is not None else None
         al = gamma.detach().reshape(-1).float()
         # PRECISE TRUNK (round 5, the IEEE-half mode; DESIGN 5.1, tests/diag/layer_ladder.py).  With the reference's small block gammas
         # the logits are a function of the SHORTCUT path image -> [pool -> conv_s -> block sum] x depth -> COND_DNET: the residual
@@ -262,26 +114,6 @@ class ResDFn(torch.autograd.Function):
                                "ops.second_order() to differentiate its backward (the MA-GP pattern)")
         outs = ResDBwdFn.apply(dout, x, xp, h1, res, w0, w2, ws, gamma, ctx.geoms, ctx.learned, ctx.has_bs, need, _skip_wgrad())
         return tuple(outs) + (None, None, None, None, None)
-
-
-class fixed_order:
-    """Context manager: the reductions that feed activations (GroupNorm statistics, the attention query gradient) in a fixed summation
-    order (xmc_set_fixed_order: one workgroup per reduction target).  A test mode -- it costs those launches their parallelism -- that
-    makes an iteration of the attention-modulation generators repeatable, so that their gradient tests need not budget for run-to-run
-    spread."""
-
-    def __enter__(self):
-        self.was = L.load().xmc_set_fixed_order(1)
-        return self
-
-    def __exit__(self, *a):
-        L.load().xmc_set_fixed_order(self.was)
-        return False
-
-
-def debug_switch(token):
-    """True when `token` is listed in XMC_DEBUG_DISPATCH (A/B experiments; unset in production)"""
-    return token in _DEBUG_DISPATCH
 
 
 def dstem_eligible(xin, c_img, c_sc, c_out):
@@ -615,161 +447,6 @@ def res_pool_ok(h1, g2):
     """the pooled third output needs an even-sized map (the C side falls back to its own pool pass where the kernel cannot)"""
     OH, OW = g2.out_hw(h1.shape[1], h1.shape[2])
     return OH % 2 == 0 and OW % 2 == 0
-
-
-class ColSumFn(torch.autograd.Function):
-    """sum over all pixels -> f32 [C]  (bias gradients)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = x.contiguous()
-        Cc = x.shape[-1]
-        out = _zeros_f32_out(Cc, x.device)
-        L.call("xmc_colsum", _p(x), _p(out), x.numel() // Cc, Cc, _code(x.dtype), _st())
-        ctx.shape, ctx.dtype = x.shape, x.dtype
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        return g.to(ctx.dtype).expand(ctx.shape).contiguous()
-
-
-class SumPool2Fn(torch.autograd.Function):
-    """scale * (2x2 sum pool).  scale=0.25: F.avg_pool2d(x, 2) (df_gan.py:290); adjoint of Up2Fn."""
-
-    @staticmethod
-    def forward(ctx, x, scale):
-        x = x.contiguous()
-        N, H, W, Cc = x.shape
-        y = torch.empty((N, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device)
-        L.call("xmc_sumpool2", _p(x), _p(y), N, H, W, Cc, float(scale), _code(x.dtype), _st())
-        ctx.scale = scale
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return Up2Fn.apply(dy, ctx.scale), None
-
-
-class Up2Fn(torch.autograd.Function):
-    """scale * nearest x2 upsample.  scale=1: F.interpolate(scale_factor=2) (df_gan.py:202)."""
-
-    @staticmethod
-    def forward(ctx, x, scale):
-        x = x.contiguous()
-        N, H, W, Cc = x.shape
-        y = torch.empty((N, 2 * H, 2 * W, Cc), dtype=x.dtype, device=x.device)
-        L.call("xmc_upsample2", _p(x), _p(y), N, H, W, Cc, float(scale), _code(x.dtype), _st())
-        ctx.scale = scale
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return SumPool2Fn.apply(dy, ctx.scale), None
-
-
-class GapFn(torch.autograd.Function):
-    """mean over all pixels of an [N,H,W,C] map -> [N,C] (F.avg_pool2d(x,4) on 4x4: df_gan.py:165, train_gan.py:272,275)."""
-
-    @staticmethod
-    def forward(ctx, x, out_dtype):
-        x = x.contiguous()
-        N, H, W, Cc = x.shape
-        # (an f32 result is accumulated with atomics on big maps: handed over zero-filled, lib.load() has told the library so)
-        y = _zeros_f32_out((N, Cc), x.device) if out_dtype == torch.float32 else torch.empty((N, Cc), dtype=out_dtype, device=x.device)
-        L.call("xmc_global_avgpool", _p(x), _p(y), N, H * W, Cc, _code(x.dtype), _code(out_dtype), _st())
-        ctx.hw, ctx.dtype = (H, W), x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return GapBwdFn.apply(dy, ctx.hw, ctx.dtype), None
-
-
-class GapBwdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, dy, hw, dtype):
-        dy = dy.contiguous()
-        N, Cc = dy.shape
-        dx = torch.empty((N, hw[0], hw[1], Cc), dtype=dtype, device=dy.device)
-        L.call("xmc_global_avgpool_bwd", _p(dy), _p(dx), N, hw[0] * hw[1], Cc, _code(dtype), _code(dy.dtype), _st())
-        ctx.in_dtype = dy.dtype
-        return dx
-
-    @staticmethod
-    def backward(ctx, g):
-        return GapFn.apply(g, ctx.in_dtype), None, None
-
-
-class NchwToNhwc8Fn(torch.autograd.Function):
-    """[N,C<=8,H,W] f32 (module boundary, df_gan.py:127) -> [N,H,W,8] activation dtype, zero padded."""
-
-    @staticmethod
-    def forward(ctx, x, dtype, out=None):
-        _need_cuda(x)
-        x = x.contiguous().float()
-        N, Cc, H, W = x.shape
-        if out is None:
-            y = torch.empty((N, H, W, 8), dtype=dtype, device=x.device)
-        else:                      # caller-provided destination (e.g. one half of the discriminator's 2B input); written
-            # behind autograd's back (no version bump), so it must be a tensor no earlier node has saved
-            assert tuple(out.shape) == (N, H, W, 8) and out.dtype == dtype and out.is_contiguous() and out._version == 0
-            y = out
-        L.call("xmc_nchw_to_nhwc8", _p(x), _p(y), N, Cc, H, W, _code(dtype), _st())
-        ctx.c = Cc
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return Nhwc8ToNchwFn.apply(dy, ctx.c), None, None
-
-
-class Nhwc8ToNchwFn(torch.autograd.Function):
-    """[N,H,W,8] -> [N,C,H,W] f32 (the image NetG returns, df_gan.py:101-103)."""
-
-    @staticmethod
-    def forward(ctx, x, c):
-        x = x.contiguous()
-        N, H, W, _ = x.shape
-        y = torch.empty((N, c, H, W), dtype=torch.float32, device=x.device)
-        L.call("xmc_nhwc8_to_nchw", _p(x), _p(y), N, c, H, W, _code(x.dtype), _st())
-        ctx.dtype = x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return NchwToNhwc8Fn.apply(dy, ctx.dtype), None
-
-
-def _affine_fwd_raw(x, ps, slope):
-    """ps: (g0, b0) or (g0, b0, g1, b1), contiguous f32 [N, C]"""
-    N, H, W, Cc = x.shape
-    for t in ps:
-        assert t.shape == (N, Cc), (t.shape, (N, Cc))
-    y = torch.empty_like(x)
-    ptrs = [_p(t) for t in ps] + ([] if len(ps) == 4 else [None, None])
-    L.call("xmc_affine2_act_fwd", _p(x), *ptrs, _p(y), N, H * W, Cc, float(slope), _code(x.dtype), _st())
-    return y
-
-
-def _affine_bwd_raw(x, dy, ps, slope, dx_acc=None, alpha=None, dot=None, want_sumpool=False):
-    """-> dx, red [len(ps), N, C] (the gradients of ps).  ``dx_acc``: another gradient of x, added on the way out.
-    ``alpha`` / ``dot`` (f32 [1] each): dy is the UNSCALED gradient from a consumer `sum + alpha * f(y)`: dot += <dy, y>, dy *= alpha
-    (xmc_affine2_act_bwd_dot).  ``want_sumpool``: -> dx, red, 2x2 sum pool of dx (same pass)."""
-    N, H, W, Cc = x.shape
-    dx = torch.empty_like(x)
-    if dx_acc is not None:
-        dx_acc = dx_acc.contiguous()
-        assert dx_acc.shape == x.shape and dx_acc.dtype == x.dtype
-    nred = len(ps)
-    red = _zeros_f32((nred, N, Cc), x.device)
-    ptrs = [_p(t) for t in ps] + ([] if nred == 4 else [None, None])
-    rptrs = [_p(red[i]) for i in range(nred)] + ([] if nred == 4 else [None, None])
-    assert (alpha is None) == (dot is None)
-    dxp = torch.empty((N, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device) if want_sumpool else None
-    L.call("xmc_affine2_act_bwd_dot_pool", _p(x), _p(dy), *ptrs, _p(dx), *rptrs, _p(dx_acc), _p(alpha), _p(dot), _p(dxp), N, H, W, Cc,
-           float(slope), _code(x.dtype), _st())
-    return (dx, red, dxp) if want_sumpool else (dx, red)
 
 
 class Affine2LreluFn(torch.autograd.Function):

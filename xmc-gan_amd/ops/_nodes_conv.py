@@ -1,21 +1,60 @@
-"""xmc_gan_amd.ops: autograd nodes of the convolution / linear layers, the generator block end, the conditioning-MLP bank and the text front end.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
+"""xmc_gan_amd.ops, layer 4: autograd nodes of the convolution / linear layers, the generator block end, the conditioning-MLP bank
+and the text front end.  Imports `_config`, `_engine` and `_nodes_leaf`."""
 import ctypes as C
-import os
-import threading
-import weakref
 import numpy as np
 import torch
 from .. import lib as L
-from .. import prof
-from ._config import (
-    _code, _p, _skip_wgrad, _st, act_dtype, fused_blocks, pad_to)
+from ._config import _code, _p, _skip_wgrad, _st, act_dtype, pad_to
 from ._engine import (
-    _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw, _pooled_take, _upconv_dgrad_raw,
-    _upconv_fwd_raw, _zeros_f32, _zeros_f32_out)
+    _affine_bwd_raw, _affine_fwd_raw, _axpby_bwd_fused, _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw,
+    _pooled_take, _upconv_dgrad_raw, _upconv_fwd_raw, _zeros_f32, _zeros_f32_out)
+from ._nodes_leaf import CastFn, ColSumFn, MaskFn, TanhBwdFn
 
 
 # ------------------------------------------------------------------------------------------ conv / linear
+def _bias_padded(b, geom, permute=False):
+    """the bias as the kernels read it: f32, zero-padded to the stored channels.  ``permute`` (ConvFn, the one node whose layers
+    carry a `geom.row_perm`): rows in the order of the packed weight's"""
+    if b is None:
+        return None
+    bp = b.detach().float()
+    if permute and geom.row_perm is not None:
+        bp = bp.index_select(0, geom.perm_dev(b.device).long())
+    cd_p = pad_to(geom.cout, 8)
+    if bp.numel() < cd_p:
+        bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
+    return bp.contiguous()
+
+
+def _act_bwd(dy, y, act, dtype):
+    """dy in front of a layer's activation (y: the layer's saved output), in the dtype of the layer's operands"""
+    dy = dy.contiguous()
+    if act in (L.ACT_LRELU, L.ACT_RELU):
+        dy = MaskFn.apply(dy, y, 0.2 if act == L.ACT_LRELU else 0.0)
+    elif act == L.ACT_TANH:
+        dy = TanhBwdFn.apply(dy, y)
+    return dy if dy.dtype == dtype else CastFn.apply(dy, dtype)
+
+
+def _wgrad_bias_raw(ctx, x, dy, w, geom, scale=None, up=False):
+    """(dw, db) of a first-order node with inputs (x, w, b, ...): the bias gradient rides on the weight-gradient launch where both
+    are asked for and is the column sums of dy where it alone is; (None, None) inside `no_wgrad()`"""
+    dw = db = None
+    if not _skip_wgrad():
+        want_b = ctx.has_b and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            r = _conv_wgrad_raw(x, dy, geom, scale=scale, up=up, want_bias=want_b)
+            dw, db = r if want_b else (r, None)
+            dw = dw.view(w.shape)
+        elif want_b:
+            db = ColSumFn.apply(dy)
+            if scale is not None:
+                db = db * scale
+        if db is not None:
+            db = db[: geom.cout]
+    return dw, db
+
+
 class ConvFn(torch.autograd.Function):
     """y = act(conv2d(x, w) + b).  F.conv2d / nn.Linear call sites: df_gan.py:73-74,86,144,157-159,187-188,
     197,233-240,273,276,280."""
@@ -28,15 +67,7 @@ class ConvFn(torch.autograd.Function):
         x = x.contiguous()
         # `out` is written behind autograd's back (no version bump): it must be a tensor no earlier node has saved
         assert out is None or out._version == 0, "ConvFn(out=): the destination must be a fresh tensor"
-        bp = None
-        if b is not None:
-            cd_p = pad_to(geom.cout, 8)
-            bp = b.detach().float()
-            if geom.row_perm is not None:
-                bp = bp.index_select(0, geom.perm_dev(b.device).long())
-            if bp.numel() < cd_p:
-                bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
-            bp = bp.contiguous()
+        bp = _bias_padded(b, geom, permute=True)
         if pair and x.dtype != torch.float32 and act == L.ACT_NONE and not want_pool and out is None:
             y = _conv1x1_pair_raw(x, w, bp, geom, out_dtype)
         else:
@@ -58,24 +89,16 @@ class ConvFn(torch.autograd.Function):
             return None, None, None, None, None, None, None, None, None
         x, w, y = ctx.saved_tensors
         geom = ctx.geom
-        dy = dy.contiguous()
-        if ctx.act in (L.ACT_LRELU, L.ACT_RELU):
-            dy = MaskFn.apply(dy, y, 0.2 if ctx.act == L.ACT_LRELU else 0.0)
-        elif ctx.act == L.ACT_TANH:
-            dy = TanhBwdFn.apply(dy, y)
-        if dy.dtype != x.dtype:
-            dy = CastFn.apply(dy, x.dtype)
+        dy = _act_bwd(dy, y, ctx.act, x.dtype)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = ConvDgradFn.apply(dy, w, geom, (x.shape[1], x.shape[2]), x.dtype)
         if not _skip_wgrad():
             want_b = ctx.has_b and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                if want_b:                      # bias gradient rides on the weight-gradient launch
-                    dw, db = ConvWgradBiasFn.apply(x, dy, geom)
-                    dw = dw.view(w.shape)
-                else:
-                    dw = ConvWgradFn.apply(x, dy, geom).view(w.shape)
+            if ctx.needs_input_grad[1]:         # (the bias gradient rides on the weight-gradient launch)
+                r = ConvWgradFn.apply(x, dy, geom, want_b)
+                dw, db = r if want_b else (r, None)
+                dw = dw.view(w.shape)
             elif want_b:
                 db = ColSumFn.apply(dy)
             if db is not None:
@@ -113,10 +136,7 @@ class PairConvFn(torch.autograd.Function):
             return None, None, None, None
         xh, w, y = ctx.saved_tensors
         geom = ctx.geom
-        dy = dy.contiguous()
-        if ctx.act in (L.ACT_LRELU, L.ACT_RELU):
-            dy = MaskFn.apply(dy, y, 0.2 if ctx.act == L.ACT_LRELU else 0.0)
-        dy = CastFn.apply(dy, xh.dtype)
+        dy = _act_bwd(dy, y, ctx.act, xh.dtype)
         dx = CastFn.apply(ConvDgradFn.apply(dy, w, geom, (xh.shape[1], xh.shape[2]), xh.dtype), torch.float32) if ctx.needs_input_grad[0] else None
         dw = ConvWgradFn.apply(xh, dy, geom).view(w.shape) if (ctx.needs_input_grad[1] and not _skip_wgrad()) else None
         return dx, dw, None, None
@@ -153,18 +173,21 @@ class ConvDgradFn(torch.autograd.Function):
 
 
 class ConvWgradFn(torch.autograd.Function):
-    """dw of ConvFn; bilinear in (x, dy)."""
+    """dw of ConvFn; bilinear in (x, dy).  ``want_bias``: returns (dw, db) -- the bias gradient (column sums of dy) comes out of the
+    same kernel launch and is not differentiable."""
 
     @staticmethod
-    def forward(ctx, x, dy, geom):
+    def forward(ctx, x, dy, geom, want_bias=False):
         x, dy = x.contiguous(), dy.contiguous()
-        gw = _conv_wgrad_raw(x, dy, geom)
+        r = _conv_wgrad_raw(x, dy, geom, want_bias=want_bias)
         ctx.geom = geom
         ctx.save_for_backward(x, dy)
-        return gw
+        if want_bias:
+            ctx.mark_non_differentiable(r[1])
+        return r
 
     @staticmethod
-    def backward(ctx, ggw):
+    def backward(ctx, ggw, _ggb=None):
         x, dy = ctx.saved_tensors
         geom = ctx.geom
         ggw = ggw.contiguous().view(geom.cout, geom.cin // geom.groups, geom.k, geom.k)
@@ -173,32 +196,7 @@ class ConvWgradFn(torch.autograd.Function):
             dx = ConvDgradFn.apply(dy, ggw, geom, (x.shape[1], x.shape[2]), x.dtype)
         if ctx.needs_input_grad[1]:
             ddy = ConvFn.apply(x, ggw, None, geom, L.ACT_NONE, dy.dtype)
-        return dx, ddy, None
-
-
-class ConvWgradBiasFn(torch.autograd.Function):
-    """ConvWgradFn that also returns the bias gradient (column sums of dy) from the same kernel launch."""
-
-    @staticmethod
-    def forward(ctx, x, dy, geom):
-        x, dy = x.contiguous(), dy.contiguous()
-        gw, gb = _conv_wgrad_raw(x, dy, geom, want_bias=True)
-        ctx.geom = geom
-        ctx.save_for_backward(x, dy)
-        ctx.mark_non_differentiable(gb)
-        return gw, gb
-
-    @staticmethod
-    def backward(ctx, ggw, _ggb):
-        x, dy = ctx.saved_tensors
-        geom = ctx.geom
-        ggw = ggw.contiguous().view(geom.cout, geom.cin // geom.groups, geom.k, geom.k)
-        dx = ddy = None
-        if ctx.needs_input_grad[0]:
-            dx = ConvDgradFn.apply(dy, ggw, geom, (x.shape[1], x.shape[2]), x.dtype)
-        if ctx.needs_input_grad[1]:
-            ddy = ConvFn.apply(x, ggw, None, geom, L.ACT_NONE, dy.dtype)
-        return dx, ddy, None
+        return dx, ddy, None, None
 
 
 class UpConvFn(torch.autograd.Function):
@@ -208,14 +206,7 @@ class UpConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, geom):
         x = x.contiguous()
-        bp = None
-        if b is not None:
-            cd_p = pad_to(geom.cout, 8)
-            bp = b.detach().float()
-            if bp.numel() < cd_p:
-                bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
-            bp = bp.contiguous()
-        y = _upconv_fwd_raw(x, w, bp, geom, L.ACT_NONE, x.dtype)
+        y = _upconv_fwd_raw(x, w, _bias_padded(b, geom), geom, L.ACT_NONE, x.dtype)
         ctx.geom, ctx.has_b = geom, b is not None
         ctx.save_for_backward(x, w)
         return y
@@ -226,64 +217,10 @@ class UpConvFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         geom = ctx.geom
         dy = dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _upconv_dgrad_raw(dy, w, geom, x.dtype)
-        if not _skip_wgrad():
-            want_b = ctx.has_b and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                # the weight gradient is taken w.r.t. the original 3x3 taps: wgrad kernel reading x through the x2 upsample
-                r = _conv_wgrad_raw(x, dy, geom, up=True, want_bias=want_b)
-                dw, db = (r if want_b else (r, None))
-                dw = dw.view(w.shape)
-            elif want_b:
-                db = ColSumFn.apply(dy)
-            if db is not None:
-                db = db[: geom.cout]
+        dx = _upconv_dgrad_raw(dy, w, geom, x.dtype) if ctx.needs_input_grad[0] else None
+        # the weight gradient is taken w.r.t. the original 3x3 taps: wgrad kernel reading x through the x2 upsample
+        dw, db = _wgrad_bias_raw(ctx, x, dy, w, geom, up=True)
         return dx, dw, db, None
-
-
-def _axpby_bwd_fused(dy, b, alpha, up, ymask=None, want_db=True):
-    """(da, db, dalpha) of a + alpha*b / up2(a) + alpha*b from one pass over dy and b (not differentiable again).
-    ``ymask``: the forward applied LeakyReLU to the sum; dy is multiplied by LeakyReLU'(y) first.  ``want_db`` False: alpha*dy
-    is not written (db is None); the caller hands alpha to the consumers of db instead."""
-    dy = dy.contiguous()
-    N, OH, OW, Cc = dy.shape
-    H, W = (OH // 2, OW // 2) if up else (OH, OW)
-    al = alpha.detach().reshape(-1).float()
-    db = torch.empty_like(dy) if want_db else None
-    da = torch.empty((N, H, W, Cc), dtype=dy.dtype, device=dy.device) if (up or ymask is not None) else None
-    dot = _zeros_f32_out(1, dy.device)
-    L.call("xmc_axpby_bwd", _p(dy), _p(b), _p(al), _p(db), _p(da), _p(dot), N, H, W, Cc, 1 if up else 0, _p(ymask), _code(dy.dtype), _st())
-    return da, db, dot.reshape(alpha.shape).to(alpha.dtype)
-
-
-class AxpbyUpFn(torch.autograd.Function):
-    """up2(a) + alpha*b without materialising up2(a): the block output `upsample(shortcut) + gamma*residual`."""
-
-    @staticmethod
-    def forward(ctx, a, b, alpha, lrelu=False):
-        a, b = a.contiguous(), b.contiguous()
-        N, H, W, Cc = a.shape
-        assert b.shape == (N, 2 * H, 2 * W, Cc)
-        al = alpha.detach().reshape(-1).float()
-        y = torch.empty_like(b)
-        L.call("xmc_axpby_up_lrelu" if lrelu else "xmc_axpby_up", _p(a), _p(b), _p(al), _p(y), N, H, W, Cc, _code(a.dtype), _st())
-        ctx.lrelu = lrelu
-        ctx.save_for_backward(b, alpha, y if lrelu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        b, alpha, y = ctx.saved_tensors
-        if not torch.is_grad_enabled() and all(ctx.needs_input_grad[:3]) and fused_blocks():
-            return _axpby_bwd_fused(dy, b, alpha, up=True, ymask=y) + (None,)      # first-order: one pass over dy and b
-        if ctx.lrelu:
-            dy = MaskFn.apply(dy.contiguous(), y, 0.2)
-        da = SumPool2Fn.apply(dy, 1.0) if ctx.needs_input_grad[0] else None
-        db = ScaleFn.apply(dy, alpha) if ctx.needs_input_grad[1] else None
-        dal = DotFn.apply(dy, b).reshape(alpha.shape) if ctx.needs_input_grad[2] else None
-        return da, db, dal, None
 
 
 class ConvAxpbyUpFn(torch.autograd.Function):
@@ -294,13 +231,7 @@ class ConvAxpbyUpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, w, b, geom, sc_lo, gamma):
         h, sc_lo = h.contiguous(), sc_lo.contiguous()
-        bp = None
-        if b is not None:
-            cd_p = pad_to(geom.cout, 8)
-            bp = b.detach().float()
-            if bp.numel() < cd_p:
-                bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
-            bp = bp.contiguous()
+        bp = _bias_padded(b, geom)
         al = gamma.detach().reshape(-1).float()
         y, res = _conv_fwd_raw(h, w, bp, geom, L.ACT_NONE, h.dtype, res=sc_lo, alpha=al, res_mode=2, want2=True)
         ctx.geom, ctx.has_b = geom, b is not None
@@ -318,32 +249,12 @@ class ConvAxpbyUpFn(torch.autograd.Function):
         al = gamma.detach().reshape(-1).float()
         dsc, _, dgamma = _axpby_bwd_fused(dy, res, gamma, up=True, want_db=False)
         dh = _conv_dgrad_raw(dy, w, geom, (h.shape[1], h.shape[2]), h.dtype, alpha=al) if ctx.needs_input_grad[0] else None
-        dw = db = None
-        if not _skip_wgrad():
-            want_b = ctx.has_b and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                r = _conv_wgrad_raw(h, dy, geom, scale=al, want_bias=want_b)
-                dw, db = (r if want_b else (r, None))
-                dw = dw.view(w.shape)
-            elif want_b:
-                db = ColSumFn.apply(dy) * al
-            if db is not None:
-                db = db[: geom.cout]
+        dw, db = _wgrad_bias_raw(ctx, h, dy, w, geom, scale=al)
         return dh, dw, db, None, (dsc if ctx.needs_input_grad[4] else None), (dgamma if ctx.needs_input_grad[5] else None)
 
 
 def conv_axpby_up(h, w, b, geom, sc_lo, gamma):
     return ConvAxpbyUpFn.apply(h, w, b, geom, sc_lo, gamma)
-
-
-def _bias_padded(b, geom):
-    if b is None:
-        return None
-    bp = b.detach().float()
-    cd_p = pad_to(geom.cout, 8)
-    if bp.numel() < cd_p:
-        bp = torch.nn.functional.pad(bp, (0, cd_p - bp.numel()))
-    return bp.contiguous()
 
 
 class GBlockEndFn(torch.autograd.Function):

@@ -1,21 +1,14 @@
-"""xmc_gan_amd.ops: losses (hinge, contrastive head), the concept algebra of the attention-modulation and word-attention generators, the gradient penalty.
-(One of the modules ops.py was split into in round 5; `xmc_gan_amd.ops` re-exports every name.)"""
+"""xmc_gan_amd.ops, layer 6: losses (hinge, contrastive head), the concept algebra of the attention-modulation and word-attention
+generators, the gradient penalty.  Imports `_config`, `_engine`, `_nodes_conv` and `_nodes_block`."""
 import ctypes as C
-import os
-import threading
-import weakref
 import numpy as np
 import torch
 from .. import lib as L
-from .. import prof
-from ._config import (
-    _code, _need_cuda, _p, _skip_wgrad, _st)
+from ._config import _code, _need_cuda, _p, _skip_wgrad, _st
 from ._engine import (
-    _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw, _zeros_f32, _zeros_f32_out)
-from ._nodes_conv import (
-    _gemm_group)
-from ._nodes_block import (
-    _affine_bwd_raw, _affine_fwd_raw, _attn_bwd_raw, _attn_fwd_raw, _gn_bwd_raw, _gn_fwd_raw)
+    _affine_bwd_raw, _affine_fwd_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw, _zeros_f32, _zeros_f32_out)
+from ._nodes_conv import _gemm_group
+from ._nodes_block import _attn_bwd_raw, _attn_fwd_raw, _gn_bwd_raw, _gn_fwd_raw
 
 
 # ------------------------------------------------------------------------------------------ losses
