@@ -45,7 +45,8 @@ extern "C" {
  * 12: XmcConvDesc.wpk_lo, XmcPackJob.lo, xmc_conv_pw1x1_split (a learned shortcut's 1x1 convolution on weights held as a 16-bit
  *     hi + lo pair: the precise trunk of the IEEE-half mode);
  *     xmc_gvec_fwd / _bwd, xmc_reasoner_fwd / _bwd, xmc_word_ctx_fwd / _bwd, xmc_word_keys_fwd / _bwd (the per-concept algebra of the
- *     word-attention generators, model/concept_gan.py). */
+ *     word-attention generators, model/concept_gan.py).
+ *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -634,6 +635,27 @@ int xmc_dstem_border_wgrad(const void* img, const void* dh1, float* dD, float* d
  * corrections added to image rows 0 / H-1 and columns 0 / W-1.  frag_scratch: 36 KB. */
 int xmc_dstem_dgrad(const void* dh1, const void* dsc, const float* wsets, const float* D, void* frag_scratch, void* dimg, int N, int H, int W,
                     void* stream);
+
+/* ---- differentiable augmentation of the discriminator's input images (csrc/augment.hip; not in the reference) --------------------
+ * x, y [N,H,W,8] (the first C <= 8 channels real, the rest zero padding; y != x), params f32 [N][8] = (b, s, c, tx, ty, cy, cx, 0) per
+ * image with the four geometric entries integers stored as floats, `cut` the side of the cutout square.  With u = x + b, p = mean_k u,
+ * v = s*u + (1-s)*p, m = mean(x) + b and w = c*v + (1-c)*m:  y(i, j) = w(i + ty, j + tx) where that source is inside the image and
+ * (i, j) is outside [cy, cy+cut) x [cx, cx+cut), else 0; pad channels 0.  f32 arithmetic, one rounding at the store; (0, 1, 1, 0, 0, ., .)
+ * with cut = 0 is a bit-exact copy.  H != W is fine.
+ *  sums:  parts f32 [N][XMC_DIFFAUG_PARTS] <- per-image partial sums, one per workgroup, written (no atomics, nothing to zero; only the
+ *         leading slots a map of H*W pixels needs are written, and apply reads exactly those).  transposed == 0: of x over all pixels and
+ *         channels < C; transposed != 0: of dy over the output pixels whose value reaches an input pixel (in frame, not cut).
+ *  apply: transposed == 0: y = A x + (b-term), or with linear_only != 0 just A x (b ignored: the derivative of the transposed map with
+ *         respect to dy, which is what differentiating a gradient penalty through the augmentation needs);  transposed != 0: dx = A^T dy.
+ *         parts: what sums wrote for the same tensor and direction, or NULL for rows that all have c == 1 (no colour component: the
+ *         mean has weight zero and nothing is read through the pointer).
+ * XMC_ESHAPE: C < 1, C > 8, cut < 0, a dtype code that is neither XMC_BF16 nor XMC_F32 (or N > 65535).  XMC_EALIGN: x, y or params not
+ * 16-byte aligned. */
+#define XMC_DIFFAUG_PARTS 64
+int xmc_diffaug_sums(const void* x, const float* params, float* parts, int N, int H, int W, int C, int cut, int transposed, int dtype,
+                     void* stream);
+int xmc_diffaug_apply(const void* x, const float* params, const float* parts, void* y, int N, int H, int W, int C, int cut, int transposed,
+                      int linear_only, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

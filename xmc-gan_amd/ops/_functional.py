@@ -1,7 +1,7 @@
 """xmc_gan_amd.ops, layer 7 (the last): one-line functional wrappers over the nodes.  May import every other module of the package."""
 import torch
 from ._config import act_dtype
-from ._nodes_leaf import AxpbyFn, AxpbyUpFn, CastFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, SumPool2Fn, Up2Fn
+from ._nodes_leaf import AxpbyFn, AxpbyUpFn, CastFn, DiffAugFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, SumPool2Fn, Up2Fn
 from ._nodes_conv import UpConvFn
 from ._nodes_block import Affine2LreluFn, AttnPoolFn, GroupNormFn
 from ._nodes_loss import ContrastiveFn, HingeFn
@@ -75,3 +75,9 @@ def contrastive(a, b, labels=None, inv_num_pos=None):
 
 def cast(x, dtype):
     return CastFn.apply(x, dtype)
+
+
+def diffaug(x_nhwc8, params, cut, color=True, channels=3):
+    """differentiable augmentation of [N,H,W,8] images from the device rows ``params`` f32 [N,8] = (b, s, c, tx, ty, cy, cx, 0) and the cutout
+    side ``cut`` (xmc_gan_amd.augment.DiffAugment draws them); ``color=False``: no row has a colour component (one launch instead of two)"""
+    return DiffAugFn.apply(x_nhwc8, params, cut, color, channels)

@@ -287,3 +287,52 @@ class Nhwc8ToNchwFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return NchwToNhwc8Fn.apply(dy, ctx.dtype), None
+
+
+# ------------------------------------------------------------------------------------------ differentiable augmentation
+def _diffaug_raw(x, params, cut, color, channels, transposed, linear_only):
+    """one sums launch (only with a colour component) and one apply launch of csrc/augment.hip"""
+    _need_cuda(x, params)
+    N, H, W, C8 = x.shape
+    if C8 != 8 or params.dtype != torch.float32 or tuple(params.shape) != (N, 8) or not params.is_contiguous():
+        raise ValueError(f"diffaug: x [N,H,W,8] and params f32 [N,8] expected, got {tuple(x.shape)} and {params.dtype} {tuple(params.shape)}")
+    y = torch.empty_like(x)
+    dims = (N, H, W, int(channels), int(cut))
+    parts = None
+    if color:
+        parts = torch.empty((N, L.DIFFAUG_PARTS), dtype=torch.float32, device=x.device)
+        L.call("xmc_diffaug_sums", _p(x), _p(params), _p(parts), *dims, int(transposed), _code(x.dtype), _st())
+    L.call("xmc_diffaug_apply", _p(x), _p(params), _p(parts), _p(y), *dims, int(transposed), int(linear_only), _code(x.dtype), _st())
+    return y
+
+
+class DiffAugFn(torch.autograd.Function):
+    """y = A x + (b-term): brightness, saturation, contrast, integer translation with zero fill and cutout of [N,H,W,8] images, per image
+    from its row (b, s, c, tx, ty, cy, cx, 0) of the device tensor ``params`` (xmc_gan_hip.h: xmc_diffaug_apply).  ``linear_only``: A x
+    alone, the form the backward node's own backward takes.  ``color=False`` promises c == 1 in every row and skips the sums launch."""
+
+    @staticmethod
+    def forward(ctx, x, params, cut, color=True, channels=3, linear_only=False):
+        x = x.contiguous()
+        ctx.params, ctx.args = params, (cut, color, channels)        # (params: a plain attribute, it takes no gradient and the
+        return _diffaug_raw(x, params, cut, color, channels, False, linear_only)      # sampler rewrites it in place between iterations)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = DiffAugBwdFn.apply(dy, ctx.params, *ctx.args) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None, None
+
+
+class DiffAugBwdFn(torch.autograd.Function):
+    """dx = A^T dy (the transposed sums / apply kernels); linear in dy with derivative A, so its backward is `DiffAugFn` without the b-term."""
+
+    @staticmethod
+    def forward(ctx, dy, params, cut, color=True, channels=3):
+        dy = dy.contiguous()
+        ctx.params, ctx.args = params, (cut, color, channels)
+        return _diffaug_raw(dy, params, cut, color, channels, True, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        dg = DiffAugFn.apply(g, ctx.params, *ctx.args, True) if ctx.needs_input_grad[0] else None
+        return dg, None, None, None, None

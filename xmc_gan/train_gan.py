@@ -38,6 +38,7 @@ from xmc_gan.utils.logger import setup_logger
 from xmc_gan.utils.miscc import count_params
 from xmc_gan.utils.visual import ScalarLog, fid_between, flush_saves, save_image, save_image_async, to_uint8_hwc
 from xmc_gan_amd import ops, parallel
+from xmc_gan_amd.augment import DiffAugment, parse_policy
 from xmc_gan_amd.optim import HipAdam, ParamEMA
 
 _GEN_ARCH = {"DF_GEN": DF_GEN, "CONCEPT_IN_DF_GEN": CONCEPT_IN_DF_GEN, "CONCEPT_OUT_DF_GEN": CONCEPT_OUT_DF_GEN,
@@ -77,6 +78,9 @@ def parse_args(argv=None):
                              'the per-epoch sample grid, eval() and netG_ema_<epoch>.pth use it.  0 (default): off')
     parser.add_argument('--ema_start', type=int, default=0,
                         help='generator steps before the averaging starts: until then the average is a copy of the weights')
+    parser.add_argument('--diffaug', type=str, default='',
+                        help="differentiable augmentation of every image the discriminator sees: comma list out of color, translation, "
+                             "cutout (typical: all three).  '' (default): off")
     return parser.parse_args(argv)
 
 
@@ -131,8 +135,9 @@ def img_loss(real_imgs, fake_imgs, labels, b_global):
 class StepOptions:
     """Engine-side switches of an iteration (not part of the reference cfg)."""
 
-    def __init__(self, gather_negatives=False, graph=False, log_each_step=True, ema=None):
+    def __init__(self, gather_negatives=False, graph=False, log_each_step=True, ema=None, diffaug=None):
         self.gather_negatives = gather_negatives
+        self.diffaug = diffaug                # xmc_gan_amd.augment.DiffAugment: netD sees augmented images only; train() refreshes its rows
         self.ema = ema                        # xmc_gan_amd.optim.ParamEMA of the generator: one update per applied generator step
         self.graph = graph                    # train(): replay the iteration as hipGraphs (xmc_gan_amd.graph.GraphedIteration)
         self.log_each_step = log_each_step    # train(): read the four logged losses back after every generator step
@@ -196,9 +201,21 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
     cuts = [] if (parallel.active() and isinstance(netD, DF_DISC) and netD.cut_block() is not None
                   and not ops.debug_switch('no_dp_overlap')) else None
     netD.cut_sink = cuts
+    # differentiable augmentation (opts.diffaug; not in the reference): EVERY image netD sees below goes through ops.diffaug first, with the
+    # rows of the sampler's static device tensor that belong to the pass.  `out['fake']`, the sample grids and eval() keep the plain images.
+    aug = opts.diffaug
+    if aug is not None and aug.batch != batch_size:
+        raise ValueError(f'DiffAugment was built for batches of {aug.batch}, got {batch_size}')
+
+    def augmented_features(x, x_h, rows):
+        """netD's features of the augmented images: x NCHW, x_h the same in the engine layout (or None)"""
+        if isinstance(netD, DF_DISC):
+            return netD(None, nhwc8=aug(x_h if x_h is not None else ops.to_nhwc8(x), rows))
+        return netD(ops.to_nchw(aug(ops.to_nhwc8(x), rows), x.shape[1]))       # a discriminator without an engine-layout entrance
     if imgs_h is not None and fake_h is not None and not cfg.DISC.SPEC_NORM and ops.fused_blocks() and not ops.debug_switch('no_d2b'):
         B = batch_size
-        feats = netD(None, nhwc8=both_h if both_h is not None else torch.cat((imgs_h, fake_h.detach())))
+        x2b = both_h if both_h is not None else torch.cat((imgs_h, fake_h.detach()))
+        feats = netD(None, nhwc8=x2b if aug is None else aug(x2b, aug.rows_d()))
         real_features, fake_features = feats[:B], feats[B:]
         ps_d = psent_embs.detach()
         rows = [feats, real_features[:B - 1]] if T.RMIS_LOSS else [feats]
@@ -213,10 +230,17 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
             mis_loss = mis_loss + errD_mismatch
             out['errD_mismatch'] = errD_mismatch.detach()
     else:
-        real_features = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
+        if aug is not None:
+            real_features = augmented_features(imgs, imgs_h, aug.rows_real())
+        else:
+            real_features = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
         outputs_real = netD.COND_DNET(real_features, sent_embs=psent_embs.detach())
         errD_real = ops.hinge(outputs_real[0], -1.0)
-        fake_features = netD(fake.detach(), nhwc8=fake_h.detach()) if fake_h is not None and imgs_h is not None else netD(fake.detach())
+        if aug is not None:
+            fake_features = augmented_features(fake.detach(), fake_h.detach() if fake_h is not None and imgs_h is not None else None,
+                                               aug.rows_fake())
+        else:
+            fake_features = netD(fake.detach(), nhwc8=fake_h.detach()) if fake_h is not None and imgs_h is not None else netD(fake.detach())
         outputs_fake = netD.COND_DNET(fake_features, sent_embs=psent_embs.detach())
         errD_fake = ops.hinge(outputs_fake[0], 1.0)
         mis_loss = errD_fake
@@ -277,7 +301,8 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
         # (ops.ResDBwdFn); with spectral norm the blocks are composed from the fine-grained Functions as before
         # ops.second_order(): the blocks keep their residual branch (not just its sign bits) for the linearised forward
         with (ops.composable() if cfg.DISC.SPEC_NORM else contextlib.nullcontext()), ops.second_order():
-            features = netD(interpolated)
+            # (augmented: the penalty is taken where the discriminator is evaluated, and differentiated through the augmentation)
+            features = netD(interpolated) if aug is None else augmented_features(interpolated, None, aug.rows_real())
             o = netD.COND_DNET(features, sent_inter)
         s_in = ops.gp_inner_scale()    # IEEE-half mode: the inner backward runs on s_in x ones, the penalty divides it out
         with ops.no_wgrad():           # first-order pass only needs d(logit)/d(inputs)
@@ -305,14 +330,20 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
     if it_state['i'] % T.N_CRITIC == 0:
         _set_requires_grad(netD, False)          # D's weight grads would be discarded (zero_grad at 226-227)
         try:
-            features = netD(fake, nhwc8=fake_h) if fake_h is not None and imgs_h is not None else netD(fake)
+            if aug is not None:
+                features = augmented_features(fake, fake_h if fake_h is not None and imgs_h is not None else None, aug.rows_g())
+            else:
+                features = netD(fake, nhwc8=fake_h) if fake_h is not None and imgs_h is not None else netD(fake)
             outputs = netD.COND_DNET(features, sent_embs=psent_embs)
             errG_fake = -outputs[0].float().mean()
             enc_loss = 0.0
             real_pooled = fake_pooled = None
             if E.DISC:
                 with torch.no_grad():
-                    real_again = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
+                    if aug is not None:                  # the same rows as the generated images it is compared with
+                        real_again = augmented_features(imgs, imgs_h, aug.rows_g())
+                    else:
+                        real_again = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
                     real_pooled = ops.global_avgpool(real_again.permute(0, 2, 3, 1).contiguous())
                 fake_pooled = ops.global_avgpool(features.permute(0, 2, 3, 1).contiguous())
             # what the contrastive terms of this step compare across ranks, all-gathered in ONE collective (a seam of the captured iteration each)
@@ -479,7 +510,9 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
 
     ``opts.ema`` (a `ParamEMA` of ``netG``, ``--ema_decay``): the per-epoch grid and `eval` sample from the averaged weights,
     written into a second, eval-mode generator that exists for nothing else (the captured iteration never sees it); checkpoints
-    add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training."""
+    add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training.
+
+    ``opts.diffaug`` (a `DiffAugment`, ``--diffaug``): its rows are redrawn before every iteration, graphed or eager."""
     device = next(netG.parameters()).device
     opts = opts or StepOptions()
     ema = opts.ema
@@ -520,6 +553,8 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
                 save_image(imgs_host, f'{img_dir}/imgs.png', normalize=True, scale_each=True)
             noise = torch.randn(mask.size(0), cfg.TRAIN.NOISE_DIM).to(device, non_blocking=True)   # CPU generator, as upstream (197-198)
             inputs = (imgs, sent_embs, words_embs, mask, noise)
+            if opts.diffaug is not None:         # new augmentation rows, outside any capture: the replayed kernels read them from the device
+                opts.diffaug.refresh()
             if use_graph and graphed is None:
                 from xmc_gan_amd.graph import GraphedIteration
                 graphed = GraphedIteration(step_fn, inputs, n_critic=cfg.TRAIN.N_CRITIC, warmup=2)
@@ -664,6 +699,10 @@ def main(argv=None):
     args = parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0 or args.ema_start < 0:
         raise SystemExit('--ema_decay must be in [0, 1) and --ema_start >= 0')
+    try:
+        aug_policy = parse_policy(args.diffaug)
+    except ValueError as e:
+        raise SystemExit(f'--diffaug: {e}')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -769,11 +808,20 @@ def main(argv=None):
             else:
                 logger.info(f'no netG_ema_{state_epoch:03d}.pth / ema_state.pth in {model_dir}: the EMA starts from netG_{state_epoch:03d}.pth')
 
+    # augmentation of the discriminator's inputs (--diffaug): one sampler, created before any capture.  Its draws come from (seed, rank) and,
+    # on a resume, from (seed, rank, epoch): a resumed run does not continue the interrupted run's draws, it starts a stream of its own
+    aug = None
+    if aug_policy:
+        aug = DiffAugment(','.join(aug_policy), cfg.TRAIN.BATCH_SIZE, cfg.IMG.SIZE, cfg.IMG.SIZE, device, args.seed, rank)
+        if state_epoch != 0:
+            aug.seed(args.seed, rank, state_epoch)
+        logger.info(f'DiffAugment on the discriminator inputs: {",".join(aug.policy)}')
+
     writer = ScalarLog(log_dir, args.log_type, run_name=cfg.CONFIG_NAME) if rank == 0 else None
     last = train(train_loader=train_loader, test_loader=test_loader, state_epoch=state_epoch, text_encoder=text_encoder,
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
                  opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
-                                  ema=ema),
+                                  ema=ema, diffaug=aug),
                  img_dir=img_dir if rank == 0 else None, writer=writer)
     if writer is not None:
         writer.close()
