@@ -46,7 +46,8 @@ extern "C" {
  *     hi + lo pair: the precise trunk of the IEEE-half mode);
  *     xmc_gvec_fwd / _bwd, xmc_reasoner_fwd / _bwd, xmc_word_ctx_fwd / _bwd, xmc_word_keys_fwd / _bwd (the per-concept algebra of the
  *     word-attention generators, model/concept_gan.py).
- *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip). */
+ *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip);
+ *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -656,6 +657,25 @@ int xmc_diffaug_sums(const void* x, const float* params, float* parts, int N, in
                      void* stream);
 int xmc_diffaug_apply(const void* x, const float* params, const float* parts, void* y, int N, int H, int W, int C, int cut, int transposed,
                       int linear_only, int dtype, void* stream);
+
+/* ---- generated images as uint8 pixels (csrc/image.hip; the host code of utils/visual.py as device passes) ---------------------------
+ * x: engine image [N,H,W,8], element type `dtype` (XMC_BF16 = this build's 16-bit format, or XMC_F32); channels 0..2 are read, 3..7
+ * ignored.  f32 arithmetic, every operation rounded on its own, so the bytes EQUAL what the numpy code gives.  Any N, H, W >= 1 (H*W <= 2^30).
+ * The uint8 outputs may start at any byte address (unaligned leading / trailing pixels are written one by one, the body as aligned 32-bit
+ * words); exactly 3*N*H*W bytes (3*Hg*Wg for the grid) are written.
+ * XMC_EINVAL: a NULL pointer, a dtype code that is neither XMC_BF16 nor XMC_F32.  XMC_ESHAPE: N, H, W or nrow < 1, padding < 0.
+ * XMC_EALIGN: x not 16-byte aligned, parts not 4-byte aligned.
+ *
+ * to_u8: y [N,H,W,3] = trunc((x + 1) * 127.5), clamped to [0, 255], NaN -> 0: what eval() writes (reference train_gan.py:366-379). */
+int xmc_image_to_u8(const void* x, uint8_t* y, int N, int H, int W, int dtype, void* stream);
+/* minmax: per-image partial (min, max) over channels 0..2: parts [N][XMC_DIFFAUG_PARTS][2] f32, slots [0, min(64, ceil(H*W/1024))) written,
+ * one per workgroup, no atomics (the scheme of the augmentation's sums pass). */
+int xmc_image_minmax(const void* x, float* parts, int N, int H, int W, int dtype, void* stream);
+/* grid_u8: the PNG that utils/visual.save_image(x, normalize=True, scale_each=True) encodes, as uint8 [Hg,Wg,3]: per image, with (lo, hi)
+ * from `parts` as minmax wrote them, g = clamp((x - lo) / max(hi - lo, 1e-5), 0, 1), u8 = trunc(clamp(g * 255 + 0.5, 0, 255)).
+ * xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = (H + padding) * ymaps + padding, Wg likewise; N == 1: the bare image, no padding
+ * (make_grid's special case).  Writes EVERY byte of the grid (padding and empty cells = 0), so the caller zeroes nothing. */
+int xmc_image_grid_u8(const void* x, const float* parts, uint8_t* grid, int N, int H, int W, int nrow, int padding, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 this same module, and from which the later node modules build theirs.  Imports `_config` and `_engine`."""
 import torch
 from .. import lib as L
-from ._config import _code, _need_cuda, _p, _st, fused_blocks
+from ._config import _code, _need_cuda, _p, _st, act_dtype, fused_blocks
 from ._engine import _axpby_bwd_fused, _cast_raw, _zeros_f32_out
 
 
@@ -287,6 +287,57 @@ class Nhwc8ToNchwFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return NchwToNhwc8Fn.apply(dy, ctx.dtype), None
+
+
+# ------------------------------------------------------------------------------------------ images as uint8 pixels (csrc/image.hip)
+def _image_arg(x8, what):
+    """the engine-layout image of the two wrappers below, checked: they are plain functions outside autograd"""
+    _need_cuda(x8)
+    if x8.dim() != 4 or x8.shape[-1] != 8:
+        raise ValueError(f"{what}: an engine-layout image [N,H,W,8] expected, got {tuple(x8.shape)}")
+    if x8.requires_grad:
+        raise ValueError(f"{what} is not differentiable: detach the image first")
+    if x8.dtype != act_dtype():
+        raise TypeError(f"{what}: {x8.dtype} image in the {act_dtype()} mode (ops.set_precision)")
+    return x8.contiguous()
+
+
+def _u8_out(out, shape, device, what):
+    """the uint8 destination: a new tensor, or the caller's (any byte address: the kernels ask for no alignment of it)"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what}: out must be a contiguous uint8 {tuple(shape)} tensor on {device}")
+    return out
+
+
+def image_to_u8(x8, out=None):
+    """[N,H,W,8] -> uint8 [N,H,W,3] = trunc((x + 1) * 127.5): the bytes of `utils.visual.to_uint8_hwc`, made on the device"""
+    x8 = _image_arg(x8, "image_to_u8")
+    N, H, W, _ = x8.shape
+    y = _u8_out(out, (N, H, W, 3), x8.device, "image_to_u8")
+    L.call("xmc_image_to_u8", _p(x8), _p(y), N, H, W, _code(x8.dtype), _st())
+    return y
+
+
+def image_grid_u8(x8, nrow=8, padding=2, out=None):
+    """[N,H,W,8] -> uint8 [Hg,Wg,3]: the bytes `utils.visual.save_image(x, normalize=True, scale_each=True)` encodes (every image min-max
+    scaled on its own, `nrow` per row, `padding` black pixels around each; one image: the image alone).  Two launches: the per-image
+    partial (min, max), then the grid, which writes every byte of it.  ``out``: a contiguous uint8 destination of the grid's size."""
+    x8 = _image_arg(x8, "image_grid_u8")
+    N, H, W, _ = x8.shape
+    nrow, padding = int(nrow), int(padding)
+    if nrow < 1 or padding < 0:
+        raise ValueError(f"image_grid_u8: nrow {nrow}, padding {padding}")
+    pad = 0 if N == 1 else padding
+    xmaps = min(nrow, N)
+    ymaps = -(-N // xmaps)
+    shape = ((H + pad) * ymaps + pad, (W + pad) * xmaps + pad, 3)
+    out = _u8_out(out, shape, x8.device, "image_grid_u8")
+    parts = torch.empty((N, L.DIFFAUG_PARTS, 2), dtype=torch.float32, device=x8.device)
+    L.call("xmc_image_minmax", _p(x8), _p(parts), N, H, W, _code(x8.dtype), _st())
+    L.call("xmc_image_grid_u8", _p(x8), _p(parts), _p(out), N, H, W, nrow, padding, _code(x8.dtype), _st())
+    return out
 
 
 # ------------------------------------------------------------------------------------------ differentiable augmentation

@@ -10,6 +10,7 @@ Expected files under ``data/<DATASET_NAME>/`` (dataset.py:67-74,84-91,118-124): 
 """
 import os
 import pickle
+import re
 
 import numpy as np
 import torch
@@ -103,6 +104,21 @@ def get_img(img_path, normalize, transform=None):
 def index_to_sent(i2w_voca, caps):
     """token-id rows -> sentences, skipping the 0 padding (dataset.py:17-19)"""
     return [' '.join(i2w_voca[int(tok)] for tok in cap if int(tok) != 0) for cap in caps]
+
+
+def sent_to_index(w2i_voca, sentence, max_length):
+    """a sentence -> (int64 vector of ``max_length`` token ids padded with 0, number of tokens): the counterpart of `index_to_sent` and
+    the form `WordTextDataset.get_caption` hands out.  Lower-cased, split into ``\\w+`` runs, words that are not in the vocabulary
+    dropped, then truncated: the AttnGAN / DF-GAN preprocessing the caption pickles were built with (the reference repository reads the
+    finished pickles and does not contain this step).  A sentence without a single known word raises ValueError."""
+    toks = [int(w2i_voca[w]) for w in re.findall(r'\w+', str(sentence).lower()) if w in w2i_voca]
+    toks = [t for t in toks if t != 0]                                    # (0 is the padding / END id: never a word of a caption)
+    if not toks:
+        raise ValueError(f'no word of {sentence!r} is in the vocabulary')
+    n = min(len(toks), int(max_length))
+    padded = np.zeros(int(max_length), dtype='int64')
+    padded[:n] = toks[:n]
+    return padded, n
 
 
 # ----------------------------------------------------------------------------- datasets

@@ -111,6 +111,54 @@ def flush_saves():
         raise e
 
 
+class PngPool:
+    """PNG encoding off the caller's thread for `xmc_gan/sample.py`: ``min(8, usable cores)`` writer threads (never more than 8, no
+    process) behind a bounded queue, so the device keeps sampling while zlib works (PIL releases the interpreter lock while it
+    compresses).  ``put(uint8 [H,W,3] array, path)`` blocks while the queue is full; ``close()`` waits for every file and re-raises
+    the first error a writer met.  The arrays are not copied: the caller leaves them alone until `close()`."""
+
+    def __init__(self, workers=None):
+        import queue
+        import threading
+        try:
+            cores = len(os.sched_getaffinity(0))
+        except AttributeError:          # not on this platform
+            cores = os.cpu_count() or 1
+        n = max(1, min(8, cores if workers is None else int(workers)))
+        self.q, self.err, self._lock = queue.Queue(maxsize=8 * n), None, threading.Lock()
+        self.threads = [threading.Thread(target=self._run, name=f"xmc-gan-png-{i}", daemon=True) for i in range(n)]
+        for t in self.threads:
+            t.start()
+
+    def _run(self):
+        from PIL import Image
+        while True:
+            item = self.q.get()
+            if item is None:
+                return
+            try:
+                Image.fromarray(item[0]).save(item[1])
+            except Exception as e:          # noqa: BLE001 -- reported by close() on the caller's thread; the queue keeps draining
+                with self._lock:
+                    if self.err is None:
+                        self.err = e
+
+    def put(self, arr, path):
+        if not self.threads:
+            raise RuntimeError("PngPool is closed")
+        self.q.put((arr, str(path)))
+
+    def close(self):
+        for _ in self.threads:
+            self.q.put(None)
+        for t in self.threads:
+            t.join()
+        self.threads = []
+        if self.err is not None:
+            e, self.err = self.err, None
+            raise e
+
+
 def to_uint8_hwc(img):
     """one generated / real image in [-1, 1], [3,H,W] -> uint8 [H,W,3] the way eval() writes them ((x + 1) * 127.5, truncated;
     train_gan.py:366-379)"""
