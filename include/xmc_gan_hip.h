@@ -47,7 +47,8 @@ extern "C" {
  *     xmc_gvec_fwd / _bwd, xmc_reasoner_fwd / _bwd, xmc_word_ctx_fwd / _bwd, xmc_word_keys_fwd / _bwd (the per-concept algebra of the
  *     word-attention generators, model/concept_gan.py).
  *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip);
- *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip). */
+ *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip);
+ *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -317,6 +318,34 @@ int xmc_gru_bidir(const float* xproj, const float* w_hh, const float* b_hn, cons
                   int H, void* stream);
 int xmc_lstm_bidir(const float* xproj, const float* w_hh, const int32_t* lens, float* words, float* sent, int B, int T, int H,
                    void* stream);
+/* Frozen sentence encoder of the SBERT presets (csrc/transformer.hip): the non-GEMM operators of a RoBERTa forward (post-LayerNorm layers,
+ * learned absolute positions) and the pooling tail of SBERT_ENCODER.forward (reference model/encoder.py:50-70).  Forward only; no atomics:
+ * the same inputs give the same bytes.  `lens` int32 [B]: valid tokens of each right-padded sample, clamped to [0, T] by the kernels.
+ * `out16` (may be NULL): a second copy of the result in the build's 16-bit format, the next GEMM's operand.  H: a multiple of 64, <= 1024.
+ * XMC_ESHAPE: a size outside what is built (never a wrong result); XMC_EALIGN: a pointer that is not 16-byte aligned.
+ *
+ * roberta_embed_ln: out [B*T,H] = LN(word[ids[b,t]] + type0 + pos[p]), p = t + 1 + pad_idx for t < lens[b], pad_idx beyond
+ *   (cumsum(mask) * mask + padding_idx); ids int64 [B,T]; word [vocab,H], pos [npos,H], type0 [H] (token type 0), T + 1 + pad_idx <= npos.
+ *   An id outside [0, vocab) reads as a zero row (the host wrapper validates ids it can see).
+ * add_layernorm: out [rows,H] = LN(x [+ bias] [+ res]) * gamma + beta; one wave per row, two-pass f32 statistics over registers.
+ * attention_short: qkv f32 [B*T,3H] (rows [Q | K | V], head h in columns [64 h, 64 h + 64) of each), H = heads * 64;
+ *   out [B*T,H] (XMC_F32 or XMC_BF16) = softmax(Q K^T / 8 over keys j < lens[b]) V per (sample, head); the scores stay in registers, the
+ *   softmax is f32 with the row maximum subtracted.  Rows of padded queries (t >= lens[b]) are written as zeros.  head_dim must be 64
+ *   and 1 <= T <= 64.
+ * bias_gelu: out [rows,F] (XMC_F32 or XMC_BF16) = gelu(x + bias), gelu(a) = a/2 (1 + erf(a / sqrt 2)) (the exact form); F % 8 == 0.
+ * sbert_pool: hidden f32 [B,T,H] -> words [B,H,L] (hidden transposed, zero at t >= lens[b] and in columns T..L-1), sent [B,H] = the sum
+ *   over valid tokens / their count, times 1 / max(||.||_2, 1e-12) when `normalize`; mask uint8 [B,L] = 1 at t >= lens[b].
+ *   T <= L <= 64.  One launch. */
+int xmc_roberta_embed_ln(const int64_t* ids, const int32_t* lens, const float* word, const float* pos, const float* type0,
+                         const float* gamma, const float* beta, float* out, void* out16, int B, int T, int H, int64_t vocab, int npos,
+                         int pad_idx, float eps, void* stream);
+int xmc_add_layernorm(const float* x, const float* bias, const float* res, const float* gamma, const float* beta, float* out, void* out16,
+                      int64_t rows, int H, float eps, void* stream);
+int xmc_attention_short(const float* qkv, const int32_t* lens, void* out, int B, int T, int heads, int head_dim, int out_dtype,
+                        void* stream);
+int xmc_bias_gelu(const float* x, const float* bias, void* out, int64_t rows, int F, int out_dtype, void* stream);
+int xmc_sbert_pool(const float* hidden, const int32_t* lens, float* words, float* sent, uint8_t* mask, int B, int T, int H, int L,
+                   int normalize, void* stream);
 /* Spectral normalisation of a layer weight: the legacy torch.nn.utils.spectral_norm hook the reference's layer factories apply
  * when DISC.SPEC_NORM is set (model/modules.py:3,16-17,31-32).  W: f32 [R,C] row-major (the parameter weight_orig viewed as
  * [out, in*k*k]); u [R], v [C]: the hook's weight_u / weight_v buffers.  training != 0: one power iteration, IN PLACE

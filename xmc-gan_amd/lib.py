@@ -98,6 +98,11 @@ _SIGS = {
     "xmc_embedding_gather": [vp, vp, vp, i64, i32, i64, vp],
     "xmc_lstm_bidir": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "xmc_gru_bidir": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "xmc_roberta_embed_ln": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i32, f32, vp],
+    "xmc_add_layernorm": [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp],
+    "xmc_attention_short": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "xmc_bias_gelu": [vp, vp, vp, i64, i32, i32, vp],
+    "xmc_sbert_pool": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_spectral_sigma": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "xmc_spectral_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "xmc_colsum": [vp, vp, i64, i32, i32, vp],

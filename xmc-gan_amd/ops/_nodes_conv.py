@@ -523,6 +523,94 @@ def gru_bidir(xproj, w_hh, b_hn, lens, T):
     return words, sent
 
 
+# sentence encoder (SBERT_ENCODER: a frozen RoBERTa forward; csrc/transformer.hip).  Forward only, like the RNN front end above; the GEMMs
+# between these go through `linear`.  `out16`: also return the result in that 16-bit dtype (the next GEMM's operand), None in fp32 mode.
+def _enc_f32c(*ts):
+    for t in ts:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "f32 contiguous tensors expected"
+
+
+def _enc_out16(like, out16):
+    assert out16 in (None, torch.float32) or _code(out16) == L.H16
+    return None if out16 in (None, torch.float32) else torch.empty_like(like, dtype=out16)
+
+
+def roberta_embed_ln(ids, lens, word, pos, type0, gamma, beta, eps, pad_idx, out16=None):
+    """RobertaEmbeddings: LN(word[ids] + token_type[0] + position[p]) with p = cumsum(mask) * mask + pad_idx computed in the kernel from
+    the lengths of the right-padded batch.  ids int64 [B,T], lens int32 [B]; word [V,H], pos [P,H], type0 [H].
+    Returns f32 [B*T,H] (and its 16-bit copy when `out16` names one, else None)."""
+    if not ids.is_cuda or not word.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.roberta_embed_ln: CPU tensors are not supported (no CPU fallback)")
+    B, T = ids.shape
+    H = word.shape[1]
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
+    _enc_f32c(word, pos, type0, gamma, beta)
+    assert pos.shape[1] == H and type0.numel() == H and gamma.numel() == H and beta.numel() == H
+    out = torch.empty(B * T, H, dtype=torch.float32, device=word.device)
+    o16 = _enc_out16(out, out16)
+    L.call("xmc_roberta_embed_ln", _p(ids), _p(lens), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), _p(out), _p(o16), B, T, H,
+           word.shape[0], pos.shape[0], int(pad_idx), float(eps), _st())
+    return out, o16
+
+
+def add_layernorm(x, res, gamma, beta, eps, bias=None, out16=None):
+    """LN(x [+ bias] [+ res]) * gamma + beta over the last dimension of f32 [rows,H] (H a multiple of 64, <= 1024): one wave per row, f32
+    two-pass statistics.  Returns f32 [rows,H] and its 16-bit copy (None unless `out16` names a 16-bit dtype)."""
+    if not x.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.add_layernorm: CPU tensors are not supported (no CPU fallback)")
+    rows, H = x.shape
+    _enc_f32c(x, res, gamma, beta, bias)
+    assert res is None or res.shape == x.shape
+    assert gamma.numel() == H and beta.numel() == H and (bias is None or bias.numel() == H)
+    out = torch.empty_like(x)
+    o16 = _enc_out16(out, out16)
+    L.call("xmc_add_layernorm", _p(x), _p(bias), _p(res), _p(gamma), _p(beta), _p(out), _p(o16), rows, H, float(eps), _st())
+    return out, o16
+
+
+def attention_short(qkv, lens, B, T, heads, out_dtype=torch.float32):
+    """softmax(Q K^T / sqrt(d) + key padding mask) V per (sample, head) from the fused QKV projection f32 [B*T,3H] (rows [Q | K | V]), for
+    head dimension 64 and T <= 64; the scores never reach memory.  Rows of padded queries come back as zeros.  Returns [B*T,H]."""
+    if not qkv.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.attention_short: CPU tensors are not supported (no CPU fallback)")
+    _enc_f32c(qkv)
+    assert qkv.dim() == 2 and qkv.shape[0] == B * T and qkv.shape[1] % (3 * heads) == 0
+    d = qkv.shape[1] // (3 * heads)
+    assert d == 64 and 1 <= T <= 64, f"attention_short is built for head dimension 64 and T <= 64, got d={d}, T={T}"
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
+    out = torch.empty(B * T, heads * d, dtype=out_dtype, device=qkv.device)
+    L.call("xmc_attention_short", _p(qkv), _p(lens), _p(out), B, T, heads, d, _code(out_dtype), _st())
+    return out
+
+
+def bias_gelu(x, bias, out_dtype=torch.float32):
+    """gelu(x + bias) with the exact (erf) GELU -- Hugging Face's hidden_act "gelu" -- over f32 [rows,F], F % 8 == 0."""
+    if not x.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.bias_gelu: CPU tensors are not supported (no CPU fallback)")
+    _enc_f32c(x, bias)
+    assert x.dim() == 2 and bias.numel() == x.shape[1]
+    out = torch.empty_like(x, dtype=out_dtype)
+    L.call("xmc_bias_gelu", _p(x), _p(bias), _p(out), x.shape[0], x.shape[1], _code(out_dtype), _st())
+    return out
+
+
+def sbert_pool(hidden, lens, max_length, normalize):
+    """The tail of SBERT_ENCODER.forward (encoder.py:50-70) in one launch.  hidden f32 [B,T,H], lens int32 [B], T <= max_length <= 64.
+    Returns words_embs [B,H,max_length] (token embeddings x attention mask, zero at padding and beyond T), sent_embs [B,H] (mean over the
+    valid tokens, L2-normalised when `normalize`) and mask bool [B,max_length] (True at padding)."""
+    if not hidden.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.sbert_pool: CPU tensors are not supported (no CPU fallback)")
+    _enc_f32c(hidden)
+    B, T, H = hidden.shape
+    assert T <= max_length <= 64, f"sbert_pool is built for T <= max_length <= 64, got T={T}, max_length={max_length}"
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
+    words = torch.empty(B, H, max_length, dtype=torch.float32, device=hidden.device)
+    sent = torch.empty(B, H, dtype=torch.float32, device=hidden.device)
+    mask = torch.empty(B, max_length, dtype=torch.bool, device=hidden.device)
+    L.call("xmc_sbert_pool", _p(hidden), _p(lens), _p(words), _p(sent), _p(mask), B, T, H, max_length, int(bool(normalize)), _st())
+    return words, sent, mask
+
+
 class SpectralNormFn(torch.autograd.Function):
     """W / sigma(W) as the legacy ``torch.nn.utils.spectral_norm`` hook computes it (reference model/modules.py:3,16-17,
     31-32): in training mode ONE power iteration updates ``u`` [R] / ``v`` [C] in place (v <- normalize(W^T u),

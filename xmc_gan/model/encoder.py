@@ -6,9 +6,16 @@ its forward on the MI355X kernels: embedding gather, one f32 MFMA GEMM for the i
 both directions, and the per-sample LSTM recurrence kernel.  Forward only: the reference freezes the encoder and
 puts it in eval mode (train_gan.py:464-468).
 
-``SBERT_ENCODER`` (encoder.py:24-70) is a wrapper around the third-party ``sentence_transformers`` package and its
-pretrained checkpoint; neither is part of this build, so constructing it fails loudly.
+``SBERT_ENCODER`` (encoder.py:24-70) wraps ``sentence_transformers.SentenceTransformer('stsb-roberta-base')`` upstream: a
+byte-level BPE tokenizer, a frozen 12-layer RoBERTa-base forward and a masked mean pooling.  Here it reads a model directory
+the user supplies (``model_dir`` / ``XMC_SBERT_DIR``: config.json, weights, tokenizer files -- no third-party model code) and
+runs the forward on the MI355X: four MFMA GEMMs per layer through ``ops.linear`` and the kernels of csrc/transformer.hip
+(embedding sum + LayerNorm, fused short-sequence attention, bias + erf GELU, residual + LayerNorm, the pooling tail).
+Without a model directory constructing it fails loudly (ImportError), as before.
 """
+import json
+import os
+
 import torch
 import torch.nn as nn
 
@@ -93,9 +100,218 @@ class RNN_ENCODER(nn.Module):
         return words_embs, sent_embs, mask
 
 
+_SBERT_SUBDIRS = ("", "0_Transformer")          # the directory itself; the older sentence-transformers layout
+_SBERT_DROP = ("pooler.", "lm_head.", "classifier.", "embeddings.position_ids")
+
+
+def _sbert_find(model_dir, names):
+    for sub in _SBERT_SUBDIRS:
+        for n in names:
+            p = os.path.join(model_dir, sub, n)
+            if os.path.isfile(p):
+                return p
+    return None
+
+
+def _sbert_read_weights(model_dir):
+    """{Hugging Face key without the 'roberta.' prefix: tensor}; pooler / LM head keys dropped"""
+    st = _sbert_find(model_dir, ("model.safetensors",))
+    sd = None
+    if st is not None:
+        try:
+            from safetensors.torch import load_file
+            sd = load_file(st)
+        except ImportError:
+            sd = None
+    if sd is None:
+        pt = _sbert_find(model_dir, ("pytorch_model.bin",))
+        if pt is None:
+            what = "pytorch_model.bin (model.safetensors is there, but the safetensors package is not importable)" if st \
+                else "model.safetensors / pytorch_model.bin"
+            raise ImportError(f"SBERT_ENCODER: {model_dir} holds no {what} (looked in the directory and in 0_Transformer/)")
+        sd = torch.load(pt, map_location="cpu", weights_only=True)
+    out = {}
+    for k, v in sd.items():
+        k = k[len("roberta."):] if k.startswith("roberta.") else k
+        if not k.startswith(_SBERT_DROP):
+            out[k] = v
+    return out
+
+
 class SBERT_ENCODER(nn.Module):
-    def __init__(self, cfg):
+    """``SBERT_ENCODER(cfg, model_dir=None)``: the reference's call signature, ``forward(sents, sent_lens)`` ->
+    ``words_embs [B, H, MAX_LENGTH]``, ``sent_embs [B, H]``, ``mask [B, MAX_LENGTH]`` (True at padding).
+
+    One difference from upstream: ``words_embs`` and ``mask`` are always ``TEXT.MAX_LENGTH`` wide instead of cut to the batch's
+    longest sentence -- a static shape for the replayed iteration; the extra columns are zero and masked.
+    The weights are frozen tensors outside ``state_dict()`` (the reference never loads or saves this encoder's state); they move
+    with ``.to(device)``."""
+
+    def __init__(self, cfg, model_dir=None):
         super(SBERT_ENCODER, self).__init__()
-        raise ImportError(
-            "SBERT_ENCODER wraps sentence_transformers.SentenceTransformer and its pretrained checkpoint "
-            "(encoder.py:24-70); neither ships with this build.  Use a TEXT.ENCODER_NAME: 'RNN' preset or --synthetic.")
+        model_dir = model_dir or os.environ.get("XMC_SBERT_DIR", "")
+        if not model_dir:
+            raise ImportError(
+                "SBERT_ENCODER needs a RoBERTa model directory (config.json, model.safetensors or pytorch_model.bin, tokenizer.json or "
+                "vocab.json + merges.txt; e.g. a download of sentence-transformers/stsb-roberta-base): pass model_dir= / --sbert_dir or "
+                "set XMC_SBERT_DIR.  None is given.  Use a TEXT.ENCODER_NAME: 'RNN' preset or --synthetic otherwise.")
+        if not os.path.isdir(model_dir):
+            raise ImportError(f"SBERT_ENCODER: the model directory {model_dir} does not exist")
+        cj = _sbert_find(model_dir, ("config.json",))
+        if cj is None:
+            raise ImportError(f"SBERT_ENCODER: {model_dir} holds no config.json (looked in the directory and in 0_Transformer/)")
+        with open(cj) as f:
+            hf = json.load(f)
+        for key, want in (("model_type", "roberta"), ("hidden_act", "gelu"), ("position_embedding_type", "absolute")):
+            got = hf.get(key, "absolute" if key == "position_embedding_type" else None)
+            if got != want:
+                raise NotImplementedError(f"SBERT_ENCODER: {cj} has {key}={got!r}; the forward is built for {want!r}")
+        self.bert_norm = bool(cfg.TEXT.BERT_NORM)
+        self.pooling_mode = cfg.TEXT.POOLING_MODE
+        self.max_seq_length = int(cfg.TEXT.MAX_LENGTH)
+        if self.pooling_mode != 'MEAN':
+            raise NotImplementedError(f"TEXT.POOLING_MODE={self.pooling_mode!r} (encoder.py:20-21)")
+        H, self.nlayers = int(hf["hidden_size"]), int(hf["num_hidden_layers"])
+        self.hidden, self.heads, self.ffn = H, int(hf["num_attention_heads"]), int(hf["intermediate_size"])
+        self.eps = float(hf.get("layer_norm_eps", 1e-5))
+        self.pad_id, self.bos_id, self.eos_id = (int(hf.get(k, d)) for k, d in (("pad_token_id", 1), ("bos_token_id", 0), ("eos_token_id", 2)))
+        self.vocab, self.npos = int(hf["vocab_size"]), int(hf["max_position_embeddings"])
+        if H != cfg.TEXT.EMBEDDING_DIM:
+            raise ValueError(f"SBERT_ENCODER: {cj} has hidden_size {H}, the preset's TEXT.EMBEDDING_DIM is {cfg.TEXT.EMBEDDING_DIM}")
+        if self.heads * 64 != H or H > 1024 or self.ffn % 8 or self.max_seq_length > 64:
+            raise NotImplementedError(f"SBERT_ENCODER: the kernels are built for head dimension 64, hidden_size <= 1024, intermediate_size % 8 "
+                                      f"== 0 and TEXT.MAX_LENGTH <= 64 (got hidden {H}, {self.heads} heads, FFN {self.ffn}, MAX_LENGTH {self.max_seq_length})")
+        if self.max_seq_length + self.pad_id + 1 > self.npos:
+            raise ValueError(f"SBERT_ENCODER: max_position_embeddings {self.npos} is too small for TEXT.MAX_LENGTH {self.max_seq_length}")
+        self.model_dir = model_dir
+        self._tokenizer = None
+        self._w = self._assemble(_sbert_read_weights(model_dir), cj)
+        self.geom_qkv, self.geom_o = ops.ConvGeom(H, 3 * H, 1, 1, 0), ops.ConvGeom(H, H, 1, 1, 0)
+        self.geom_up, self.geom_down = ops.ConvGeom(H, self.ffn, 1, 1, 0), ops.ConvGeom(self.ffn, H, 1, 1, 0)
+        self.eval()
+
+    def _assemble(self, sd, cj):
+        """the tensors the forward reads, as frozen f32 Parameters (so that `ops.linear` caches their packed copies until one changes):
+        Q, K, V of a layer as one [3H, H] weight"""
+        H, F = self.hidden, self.ffn
+        w = {}
+
+        def take(key, shape):
+            if key not in sd:
+                raise ImportError(f"SBERT_ENCODER: the weights in {self.model_dir} lack {key!r}")
+            t = sd[key].detach().float().contiguous()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"SBERT_ENCODER: {key} is {tuple(t.shape)}, {cj} says {tuple(shape)}")
+            return t
+
+        frozen = lambda t: nn.Parameter(t.contiguous(), requires_grad=False)
+        e = "embeddings."
+        w["word"] = frozen(take(e + "word_embeddings.weight", (self.vocab, H)))
+        w["pos"] = frozen(take(e + "position_embeddings.weight", (self.npos, H)))
+        tt = sd.get(e + "token_type_embeddings.weight")
+        if tt is None or tt.dim() != 2 or tt.shape[1] != H:
+            raise ImportError(f"SBERT_ENCODER: the weights in {self.model_dir} lack {e}token_type_embeddings.weight [*, {H}]")
+        w["type0"] = frozen(tt[0].detach().float())
+        w["emb_g"], w["emb_b"] = frozen(take(e + "LayerNorm.weight", (H,))), frozen(take(e + "LayerNorm.bias", (H,)))
+        for i in range(self.nlayers):
+            l = f"encoder.layer.{i}."
+            a = l + "attention.self."
+            w[f"{i}.wqkv"] = frozen(torch.cat([take(a + n + ".weight", (H, H)) for n in ("query", "key", "value")], 0))
+            w[f"{i}.bqkv"] = frozen(torch.cat([take(a + n + ".bias", (H,)) for n in ("query", "key", "value")], 0))
+            for name, key, shape in (("wo", "attention.output.dense", (H, H)), ("w1", "intermediate.dense", (F, H)), ("w2", "output.dense", (H, F))):
+                w[f"{i}.{name}"] = frozen(take(l + key + ".weight", shape))
+                w[f"{i}.b{name[1:]}"] = frozen(take(l + key + ".bias", shape[:1]))
+            for name, key in (("ln1", "attention.output.LayerNorm"), ("ln2", "output.LayerNorm")):
+                w[f"{i}.{name}g"], w[f"{i}.{name}b"] = frozen(take(l + key + ".weight", (H,))), frozen(take(l + key + ".bias", (H,)))
+        return w
+
+    def _apply(self, fn, recurse=True):
+        super(SBERT_ENCODER, self)._apply(fn, recurse)
+        with torch.no_grad():
+            self._w = {k: nn.Parameter(fn(v.data).float().contiguous(), requires_grad=False) for k, v in self._w.items()}
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("SBERT_ENCODER runs frozen in eval mode (encoder.py:36,40); fine-tuning it is not built")
+        return super(SBERT_ENCODER, self).train(False)
+
+    # ------------------------------------------------------------------ host side: sentences -> token ids
+    def tokenizer(self):
+        """the directory's byte-level BPE through the `tokenizers` package (tokenizer.json, or vocab.json + merges.txt), without its own
+        truncation, padding or special tokens: `tokenize` adds those"""
+        if self._tokenizer is None:
+            try:
+                import tokenizers
+            except ImportError as e:
+                raise ImportError("SBERT_ENCODER.forward tokenizes with the `tokenizers` package, which is not importable here; "
+                                  "call forward_ids(input_ids, lengths) with ids tokenized elsewhere") from e
+            os.environ.setdefault('TOKENIZERS_PARALLELISM', 'false')           # encoder.py:28
+            tj = _sbert_find(self.model_dir, ("tokenizer.json",))
+            if tj is not None:
+                tok = tokenizers.Tokenizer.from_file(tj)
+            else:
+                vj, mt = _sbert_find(self.model_dir, ("vocab.json",)), _sbert_find(self.model_dir, ("merges.txt",))
+                if vj is None or mt is None:
+                    raise ImportError(f"SBERT_ENCODER: {self.model_dir} holds neither tokenizer.json nor vocab.json + merges.txt")
+                tok = tokenizers.Tokenizer(tokenizers.models.BPE.from_file(vj, mt))         # RoBERTa's: byte-level, no prefix space
+                tok.pre_tokenizer = tokenizers.pre_tokenizers.ByteLevel(add_prefix_space=False)
+            tok.no_truncation()
+            tok.no_padding()
+            self._tokenizer = tok
+        return self._tokenizer
+
+    def tokenize(self, sents):
+        """sentences -> (int64 [B, MAX_LENGTH] right-padded with the pad id, int64 [B] lengths): each string stripped, <s> ... </s>
+        around it, truncated to MAX_LENGTH tokens INCLUDING the two specials (what SentenceTransformer.tokenize does at
+        max_seq_length = TEXT.MAX_LENGTH, encoder.py:37,45)"""
+        tok, L = self.tokenizer(), self.max_seq_length
+        encs = tok.encode_batch([str(s).strip() for s in sents], add_special_tokens=False)
+        ids = torch.full((len(encs), L), self.pad_id, dtype=torch.int64)
+        lens = torch.empty(len(encs), dtype=torch.int64)
+        for i, e in enumerate(encs):
+            row = [self.bos_id] + list(e.ids)[:L - 2] + [self.eos_id]
+            ids[i, :len(row)] = torch.tensor(row, dtype=torch.int64)
+            lens[i] = len(row)
+        return ids, lens
+
+    # ------------------------------------------------------------------ device side
+    @torch.no_grad()
+    def forward_ids(self, input_ids, lengths):
+        """input_ids int64 [B, T] (T <= MAX_LENGTH, right-padded with the pad id), lengths [B] (tokens including <s> and </s>) ->
+        words_embs [B, H, MAX_LENGTH], sent_embs [B, H], mask [B, MAX_LENGTH]"""
+        w = self._w
+        dev = w["word"].device
+        input_ids, lengths = torch.as_tensor(input_ids), torch.as_tensor(lengths)
+        if input_ids.dim() != 2 or not 1 <= input_ids.size(1) <= self.max_seq_length or lengths.numel() != input_ids.size(0):
+            raise ValueError(f"input_ids must be [B, T <= {self.max_seq_length}] with one length per row, got {tuple(input_ids.shape)} / "
+                             f"{tuple(lengths.shape)}")
+        B, T = input_ids.shape
+        if not input_ids.is_cuda:      # host tensors: validate for free
+            if int(lengths.min()) < 1 or int(lengths.max()) > T:
+                raise ValueError("sentence lengths must lie in [1, T]")
+            if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.vocab:
+                raise IndexError("token id outside [0, vocab_size)")
+        ids = input_ids.to(dev, torch.int64, non_blocking=True).contiguous()
+        lens = lengths.to(dev, torch.int32, non_blocking=True).contiguous()
+        # GEMM operands in the engine's activation format; the residual stream x, LayerNorm, softmax and the pooling are f32 in every mode
+        dt = ops.act_dtype()
+        f32 = torch.float32
+        x, xh = ops.roberta_embed_ln(ids, lens, w["word"], w["pos"], w["type0"], w["emb_g"], w["emb_b"], self.eps, self.pad_id, out16=dt)
+        for i in range(self.nlayers):
+            g = lambda n: w[f"{i}.{n}"]
+            qkv = ops.linear(x if xh is None else xh, g("wqkv"), g("bqkv"), self.geom_qkv, out_dtype=f32)
+            ctx = ops.attention_short(qkv, lens, B, T, self.heads, out_dtype=dt)
+            att = ops.linear(ctx, g("wo"), g("bo"), self.geom_o, out_dtype=f32)
+            x, xh = ops.add_layernorm(att, x, g("ln1g"), g("ln1b"), self.eps, out16=dt)
+            up = ops.linear(x if xh is None else xh, g("w1"), None, self.geom_up, out_dtype=f32)
+            act = ops.bias_gelu(up, g("b1"), out_dtype=dt)
+            down = ops.linear(act, g("w2"), g("b2"), self.geom_down, out_dtype=f32)
+            x, xh = ops.add_layernorm(down, x, g("ln2g"), g("ln2b"), self.eps, out16=dt if i + 1 < self.nlayers else None)
+        return ops.sbert_pool(x.view(B, T, self.hidden), lens, self.max_seq_length, self.bert_norm)
+
+    def forward(self, sents, sent_lens=None, **kwargs):
+        """sents: a sequence of B strings; sent_lens (word counts upstream, used there only to sort the batch) is not needed"""
+        ids, lens = self.tokenize(sents)
+        T = int(lens.max())
+        return self.forward_ids(ids[:, :T], lens)

@@ -53,6 +53,8 @@ def parse_args(argv=None):
     parser.add_argument('--precision', type=str, default=None, choices=['bf16', 'f16', 'fp32'])
     parser.add_argument('--gpu', dest='gpu_id', type=int, default=0)
     parser.add_argument('--text_encoder', type=str, default=None, metavar='PATH', help='text encoder state dict (default: TEXT.ENCODER_DIR)')
+    parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
+                        help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (default: $XMC_SBERT_DIR)')
     # reranking
     parser.add_argument('--best_of', type=int, default=0, metavar='M',
                         help="draw M images per caption and keep the K the discriminator's conditional logit ranks highest (needs --netD)")
@@ -140,6 +142,8 @@ def _load_captions(args):
 def _text_encoder(args, device):
     if args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':       # as train_gan.main() picks them
         return SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, args.seed, device)
+    if cfg.TEXT.ENCODER_NAME == 'SBERT':      # frozen weights from its model directory: no state dict to load (the reference has none either)
+        return _TEXT_ARCH['SBERT'](cfg=cfg, model_dir=args.sbert_dir or None).to(device).eval()
     enc = _TEXT_ARCH[cfg.TEXT.ENCODER_NAME](cfg=cfg).to(device)      # (random weights come from torch.manual_seed(--seed) in main())
     path = args.text_encoder if args.text_encoder is not None else (f'{PROJ_DIR}/{cfg.TEXT.ENCODER_DIR}' if cfg.TEXT.ENCODER_DIR else '')
     if path and (args.text_encoder is not None or args.synthetic <= 0 or os.path.isfile(path)):

@@ -78,6 +78,9 @@ def parse_args(argv=None):
                              'the per-epoch sample grid, eval() and netG_ema_<epoch>.pth use it.  0 (default): off')
     parser.add_argument('--ema_start', type=int, default=0,
                         help='generator steps before the averaging starts: until then the average is a copy of the weights')
+    parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
+                        help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (config.json, weights, tokenizer '
+                             'files; default: $XMC_SBERT_DIR).  Without it the SBERT presets run with --synthetic only')
     parser.add_argument('--diffaug', type=str, default='',
                         help="differentiable augmentation of every image the discriminator sees: comma list out of color, translation, "
                              "cutout (typical: all three).  '' (default): off")
@@ -762,6 +765,10 @@ def main(argv=None):
                                                   num_workers=int(cfg.TRAIN.NUM_WORKERS))
     if args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':
         text_encoder = SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, seed, device)
+    elif cfg.TEXT.ENCODER_NAME == 'SBERT':
+        # frozen weights read from the model directory, the same on every rank: no state dict to load (TEXT.ENCODER_DIR is '' in every
+        # SBERT preset and the reference never loads one), no parameters to broadcast or freeze
+        text_encoder = SBERT_ENCODER(cfg=cfg, model_dir=args.sbert_dir or None).to(device).eval()
     else:       # train_gan.py:459-468
         text_encoder = _TEXT_ARCH[cfg.TEXT.ENCODER_NAME](cfg=cfg).to(device)
         enc_path = f'{PROJ_DIR}/{cfg.TEXT.ENCODER_DIR}'
