@@ -48,7 +48,8 @@ extern "C" {
  *     word-attention generators, model/concept_gan.py).
  *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip);
  *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip);
- *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip). */
+ *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip);
+ *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -705,6 +706,21 @@ int xmc_image_minmax(const void* x, float* parts, int N, int H, int W, int dtype
  * xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = (H + padding) * ymaps + padding, Wg likewise; N == 1: the bare image, no padding
  * (make_grid's special case).  Writes EVERY byte of the grid (padding and empty cells = 0), so the caller zeroes nothing. */
 int xmc_image_grid_u8(const void* x, const float* parts, uint8_t* grid, int N, int H, int W, int nrow, int padding, int dtype, void* stream);
+
+/* ---- FID evaluation: what is not a convolution (csrc/fid.hip; xmc_gan_amd/fid.py).  All f32 or wider, none on the training step --------
+ * resize_u8: src uint8 [N,H,W,3] (the layout xmc_image_to_u8 writes) -> dst f32 engine image [N,OH,OW,8]: bilinear, PyTorch's
+ * align_corners=False rule without antialias (src = max((dst + 0.5) * in / out - 0.5, 0), upper neighbour clamped to the edge), then
+ * 2 * (v / 255) - 1; channels 3..7 = 0.  Any H, W, OH, OW >= 1 (H*W, OH*OW <= 2^30); OH == H and OW == W gives 2 * (b / 255) - 1 exactly.
+ * XMC_EALIGN: dst not 16-byte aligned. */
+int xmc_fid_resize_u8(const uint8_t* src, float* dst, int N, int H, int W, int OH, int OW, void* stream);
+/* pool3x3: x f32 [N,H,W,C] -> y f32 [N,OH,OW,C], C % 4 == 0.  stride 1: padding 1, OH = H; stride 2: no padding, OH = (H - 3) / 2 + 1
+ * (floor; H, W >= 3 or XMC_ESHAPE).  XMC_POOL_AVG_VALID divides by the number of in-image pixels of the window (count_include_pad=False). */
+#define XMC_POOL_MAX 0
+#define XMC_POOL_AVG_VALID 1
+int xmc_pool3x3(const float* x, float* y, int N, int H, int W, int C, int mode, int stride, void* stream);
+/* moments: sum f64 [D] += column sums of x f32 [B,D]; outer f64 [D,D] += x^T x (products and sums in f64).  The caller zeroes both before
+ * the first batch.  One owner thread per output element, batch rows added in order: no atomics, bit-identical from run to run. D <= 32768. */
+int xmc_fid_moments(const float* x, double* sum, double* outer, int B, int D, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,22 +12,38 @@ from ._config import (
 
 # ------------------------------------------------------------------------------------------ geometry
 class ConvGeom:
-    """Geometry of one convolution / linear layer (square kernel k, stride s, padding p)."""
+    """Geometry of one convolution / linear layer: kernel k, stride s, padding p.  ``k`` and ``p`` are a number (square: every layer of
+    the GAN) or a (height, width) pair (the 1x7 / 7x1 / 1x3 / 3x1 layers of xmc_gan_amd.fid); kh / kw / ph / pw hold both forms, and a
+    pair that is not square leaves ``k`` / ``p`` None, so that the gradient launches, which are written for square kernels, fail on it
+    at once.  A kernel of more than MAX_TAPS taps runs as tap ranges (`_conv_fwd_raw(taps=)`); the data gradient needs k % s == 0 and
+    says so itself."""
 
-    __slots__ = ("cin", "cout", "k", "s", "p", "row_perm", "_perm_dev", "groups")
+    __slots__ = ("cin", "cout", "k", "s", "p", "row_perm", "_perm_dev", "groups", "kh", "kw", "ph", "pw")
 
     def __init__(self, cin, cout, k=1, s=1, p=0, row_perm=None, groups=1):
-        assert k * k <= L.MAX_TAPS and k % s == 0
+        self.kh, self.kw = k if isinstance(k, (tuple, list)) else (k, k)
+        self.ph, self.pw = p if isinstance(p, (tuple, list)) else (p, p)
+        assert self.kh >= 1 and self.kw >= 1 and self.kh * self.kw <= 127 and s >= 1      # XmcConvDesc.wi is an int8
         assert cin % groups == 0 and cout % groups == 0
-        self.cin, self.cout, self.k, self.s, self.p = cin, cout, k, s, p
+        self.cin, self.cout, self.s = cin, cout, s
+        self.k = self.kh if self.kh == self.kw else None
+        self.p = self.ph if self.ph == self.pw else None
         # groups > 1: nn.Conv2d(groups=g) weight [cout, cin/g, k, k]; the kernels see its block-diagonal expansion, which the
         # pack kernel writes and the gradient unpack kernel reads back (diagonal blocks only)
         self.groups = groups
         self.row_perm = row_perm          # optional LongTensor/list: packed output row r <- parameter row perm[r]
         self._perm_dev = None
 
+    @property
+    def ntaps(self):
+        return self.kh * self.kw
+
     def out_hw(self, h, w):
-        return (h + 2 * self.p - self.k) // self.s + 1, (w + 2 * self.p - self.k) // self.s + 1
+        return (h + 2 * self.ph - self.kh) // self.s + 1, (w + 2 * self.pw - self.kw) // self.s + 1
+
+    def taps(self):
+        """the forward tap table: (dh, dw, weight slice) in the weight's row-major order"""
+        return [(i - self.ph, j - self.pw, i * self.kw + j) for i in range(self.kh) for j in range(self.kw)]
 
     def perm_dev(self, device):
         if self.row_perm is None:
@@ -75,7 +91,7 @@ def _pack_shape(geom, transpose, dtype, up):
     cs_p = chan_pad(geom.cin, dtype)          # stored channels of x
     cd_p = pad_to(geom.cout, 8)               # stored channels of y
     rows, cols = (pad_to(cs_p, 32), cd_p) if transpose else (pad_to(cd_p, 32), cs_p)
-    return (16 if up else geom.k * geom.k), rows, cols
+    return (16 if up else geom.ntaps), rows, cols
 
 
 def _pack_job(wf, out, geom, transpose, up, lo=False):
@@ -84,7 +100,7 @@ def _pack_job(wf, out, geom, transpose, up, lo=False):
     j.w, j.wpk = wf.data_ptr(), out.data_ptr()
     perm = None if up else geom.perm_dev(wf.device)
     j.row_perm = perm.data_ptr() if perm is not None else None
-    j.Co, j.Ci, j.KHW = geom.cout, geom.cin, geom.k * geom.k
+    j.Co, j.Ci, j.KHW = geom.cout, geom.cin, geom.ntaps
     j.rows_pad, j.cols_pad = out.shape[1], out.shape[2]
     j.transpose, j.dtype, j.groups, j.upconv = int(transpose), _code(out.dtype), (1 if up else geom.groups), int(up)
     return j
@@ -270,13 +286,16 @@ def _upconv_dgrad_raw(dy, w, geom, in_dtype):
 
 
 def _conv_fwd_raw(x, w, bias, geom, act, out_dtype, res=None, alpha=None, up=False, res_mode=0, want2=False, want_pool=False,
-                  round_act=False, mask=None, out=None, post_act=L.ACT_NONE, want_sign=False, sc_img=None, w_lo=False):
+                  round_act=False, mask=None, out=None, post_act=L.ACT_NONE, want_sign=False, sc_img=None, w_lo=False, taps=None):
     """y = act(conv(x, w) + bias) [*alpha] [+ res]; x [N,H,W,Cs]. ``up``: x is read through a fused nearest x2.
     ``res_mode`` 2: res is [N,OH/2,OW/2,C] and read through a nearest x2.  ``want2``: also return act(conv + bias) itself (the
     branch value before alpha / res);  ``want_pool``: also return avg_pool2d(y, 2).  Extras are appended: (y[, y2][, ypool]).
     ``sc_img`` = (image [N,2 OH,2 OW,8], sc_frag, sc_bias): the residual is the composed stem's shortcut, recomputed from the image inside the
-    kernel (XmcConvDesc.sc_img, xmc_conv_ptile_scimg) -- returns None when the kernel declines the shape."""
+    kernel (XmcConvDesc.sc_img, xmc_conv_ptile_scimg) -- returns None when the kernel declines the shape.
+    ``taps`` = (lo, hi): only that range of the tap table, for a kernel of more than MAX_TAPS taps (the caller sums the ranges through ``res``)."""
     _need_cuda(x, w)
+    table = geom.taps() if taps is None else geom.taps()[taps[0]:taps[1]]
+    assert 1 <= len(table) <= L.MAX_TAPS, (geom.kh, geom.kw, taps)
     N, H, W, CS = x.shape
     sh = 1 if up else 0
     Hv, Wv = H << sh, W << sh
@@ -297,12 +316,12 @@ def _conv_fwd_raw(x, w, bias, geom, act, out_dtype, res=None, alpha=None, up=Fal
     d.N, d.SH, d.SW, d.CS = N, H, W, CS
     d.DH, d.DW, d.CD = OH, OW, cd_p
     d.MH, d.MW, d.SA, d.DA, d.src_shift = OH, OW, geom.s, 1, sh
-    d.ntaps, d.nclass, d.CDw = geom.k * geom.k, 1, wpk.shape[1]
+    d.ntaps, d.nclass, d.CDw = len(table), 1, wpk.shape[1]
     d.act, d.dtype, d.out_dtype = act, _code(x.dtype), _code(out_dtype)
     d.res_mode, d.round_act = res_mode, int(bool(round_act))
     d.groups = geom.groups
     d.post_act = post_act           # applied last, to the sum with the residual (XmcConvDesc.post_act)
-    _fill_taps(d, 0, [(kh - geom.p, kw - geom.p, kh * geom.k + kw) for kh in range(geom.k) for kw in range(geom.k)])
+    _fill_taps(d, 0, table)
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() >= cd_p, "bias must be f32 and padded to the stored channels"
     if res is not None:
@@ -337,8 +356,8 @@ def _conv_fwd_raw(x, w, bias, geom, act, out_dtype, res=None, alpha=None, up=Fal
             return None
         L.check(rc, "xmc_conv_ptile_scimg")
         return y if len(outs) == 1 else tuple(outs)
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                     f"fwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, wpk, res, mask, *outs)):
+    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * len(table),
+                     f"fwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k or f'{geom.kh}x{geom.kw}'}s{geom.s}", _nbytes(x, wpk, res, mask, *outs)):
         _igemm(d, "xmc_conv_igemm(fwd)")
     return y if len(outs) == 1 else tuple(outs)
 
@@ -412,6 +431,7 @@ def _conv_dgrad_raw(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=
     d.N, d.SH, d.SW, d.CS = N, OH, OW, CDy
     d.DH, d.DW, d.CD = H, W, cs_p
     s, k, p = geom.s, geom.k, geom.p
+    assert k is not None and p is not None and k % s == 0 and k * k <= L.MAX_TAPS, "data gradient: square kernel, k % s == 0"
     d.MH, d.MW, d.SA, d.DA, d.src_shift = H // s, W // s, 1, s, 0
     d.nclass, d.CDw = s * s, wpk.shape[1]
     d.act, d.dtype, d.out_dtype = L.ACT_NONE, _code(dy.dtype), _code(in_dtype)

@@ -340,6 +340,57 @@ def image_grid_u8(x8, nrow=8, padding=2, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ FID evaluation (csrc/fid.hip): f32, outside autograd
+def _fid_arg(x, what, dtype, dims):
+    _need_cuda(x)
+    if x.dim() != dims or x.dtype != dtype or x.requires_grad:
+        raise ValueError(f"{what}: a {dims}-d {dtype} tensor without a gradient expected, got {tuple(x.shape)} {x.dtype}")
+    return x.contiguous()
+
+
+def fid_resize_u8(u8, out_hw=None):
+    """uint8 [N,H,W,3] (what `image_to_u8` writes and PIL reads) -> f32 engine image [N,OH,OW,8]: bilinear (align_corners=False, no
+    antialias) to ``out_hw`` (None: the size it has), then 2 * (x / 255) - 1; channels 3..7 are zero"""
+    u8 = _fid_arg(u8, "fid_resize_u8", torch.uint8, 4)
+    N, H, W, c = u8.shape
+    if c != 3 or N < 1 or H < 1 or W < 1:
+        raise ValueError(f"fid_resize_u8: uint8 [N,H,W,3] expected, got {tuple(u8.shape)}")
+    OH, OW = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if OH < 1 or OW < 1:
+        raise ValueError(f"fid_resize_u8: output size {OH}x{OW}")
+    y = torch.empty((N, OH, OW, 8), dtype=torch.float32, device=u8.device)
+    L.call("xmc_fid_resize_u8", _p(u8), _p(y), N, H, W, OH, OW, _st())
+    return y
+
+
+def pool3x3(x, mode, stride):
+    """3x3 pool of f32 [N,H,W,C] (C % 4 == 0).  ``mode`` 'max' or 'avg' (the sum over the window's in-image pixels divided by their number:
+    avg_pool2d(count_include_pad=False)); ``stride`` 1 (padding 1, same size) or 2 (no padding, floor((H - 3) / 2) + 1 rows)"""
+    x = _fid_arg(x, "pool3x3", torch.float32, 4)
+    if mode not in ("max", "avg") or stride not in (1, 2):
+        raise ValueError(f"pool3x3: mode {mode!r}, stride {stride}")
+    N, H, W, Cc = x.shape
+    if N < 1 or Cc < 4 or Cc % 4 or H < 1 or W < 1 or (stride == 2 and (H < 3 or W < 3)):
+        raise ValueError(f"pool3x3: {tuple(x.shape)} at stride {stride} (C % 4 == 0; stride 2 needs a whole 3x3 window)")
+    OH, OW = (H, W) if stride == 1 else ((H - 3) // 2 + 1, (W - 3) // 2 + 1)
+    y = torch.empty((N, OH, OW, Cc), dtype=torch.float32, device=x.device)
+    L.call("xmc_pool3x3", _p(x), _p(y), N, H, W, Cc, L.POOL_MAX if mode == "max" else L.POOL_AVG_VALID, stride, _st())
+    return y
+
+
+def fid_moments(feats, total, outer):
+    """total f64 [D] += column sums of feats f32 [B,D]; outer f64 [D,D] += feats^T feats, in f64 and in a fixed order (same bytes every run)"""
+    feats = _fid_arg(feats, "fid_moments", torch.float32, 2)
+    B, D = feats.shape
+    for t, shape in ((total, (D,)), (outer, (D, D))):
+        _need_cuda(t)
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != feats.device:
+            raise ValueError(f"fid_moments: accumulator {tuple(t.shape)} {t.dtype}, a contiguous f64 {shape} on {feats.device} expected")
+    if B < 1:
+        raise ValueError("fid_moments: an empty batch")
+    L.call("xmc_fid_moments", _p(feats), _p(total), _p(outer), B, D, _st())
+
+
 # ------------------------------------------------------------------------------------------ differentiable augmentation
 def _diffaug_raw(x, params, cut, color, channels, transposed, linear_only):
     """one sums launch (only with a colour component) and one apply launch of csrc/augment.hip"""

@@ -55,6 +55,11 @@ def parse_args(argv=None):
     parser.add_argument('--text_encoder', type=str, default=None, metavar='PATH', help='text encoder state dict (default: TEXT.ENCODER_DIR)')
     parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
                         help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (default: $XMC_SBERT_DIR)')
+    # scoring
+    parser.add_argument('--fid_against', type=str, default='', metavar='DIR_OR_NPZ',
+                        help='score the sampled images: FID against an image directory or an .npz statistics file -> manifest "fid"')
+    parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
+                        help='FID Inception weights for --fid_against (the pt_inception-2015-12-05-*.pth state dict; default: $XMC_FID_INCEPTION)')
     # reranking
     parser.add_argument('--best_of', type=int, default=0, metavar='M',
                         help="draw M images per caption and keep the K the discriminator's conditional logit ranks highest (needs --netD)")
@@ -86,6 +91,12 @@ def _check_args(args):
         raise SystemExit('--walk / --interp_sent need at least 2 frames')
     if args.walk and max(args.n_per_caption, args.best_of) < 2:
         raise SystemExit("--walk goes from a caption's first noise to its second: ask for --n_per_caption 2 (or more)")
+    if args.fid_against:
+        args.fid_inception = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
+        if not (os.path.isdir(args.fid_against) or (os.path.isfile(args.fid_against) and args.fid_against.endswith('.npz'))):
+            raise SystemExit(f'--fid_against: {args.fid_against} is neither an image directory nor an .npz statistics file')
+        if not args.fid_inception or not os.path.isfile(args.fid_inception):
+            raise SystemExit(f'--fid_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -209,6 +220,11 @@ def main(argv=None):
     n_grid = min(n * K, args.grid_max)
     kept = torch.empty((n_grid, S, S, 8), dtype=ops.act_dtype(), device=device) if n_grid else None      # the grid's images, engine layout
     images, pool = [], (None if args.no_png else PngPool())
+    fid_ex = fid_stats = None
+    if args.fid_against:                                             # the sampled images are scored from the device, as the bytes of the PNGs
+        from xmc_gan.utils.visual import fid_extractor
+        from xmc_gan_amd.fid import FeatureStats, frechet_distance, stats_of
+        fid_ex, fid_stats = fid_extractor(args.fid_inception, device), FeatureStats(device=device)
     cap_step = max(1, bs // M)                                       # captions per batch: about `bs` forwards' worth of images
     try:
         for c0 in range(0, n, cap_step):
@@ -224,6 +240,8 @@ def main(argv=None):
                 u8, sc = ops.image_to_u8(x8), None
             if c0 * K < n_grid:
                 kept[c0 * K:min(n_grid, c1 * K)] = x8[:n_grid - c0 * K]
+            if fid_stats is not None:
+                fid_stats.update(fid_ex(u8))
             host = u8.cpu().numpy()                                  # one copy per batch: 3 bytes per pixel
             for r in range(nc * K):
                 c, k = c0 + r // K, r % K
@@ -257,10 +275,16 @@ def main(argv=None):
         from PIL import Image
         grid = 'grid.png'
         Image.fromarray(ops.image_grid_u8(kept).cpu().numpy()).save(os.path.join(args.out, grid))
+    fid = None
+    if fid_stats is not None:
+        if fid_stats.n < 2:
+            raise SystemExit('--fid_against: a covariance needs at least two sampled images')
+        fid = frechet_distance(*stats_of(args.fid_against, fid_ex, bs), *fid_stats.finalize())
+        print(f'FID: {fid}')
     manifest = dict(checkpoint=os.path.abspath(args.checkpoint), netD=os.path.abspath(args.netD) if args.netD else None,
                     cfg=os.path.abspath(args.cfg), config_name=cfg.CONFIG_NAME, generator=cfg.GEN.ENCODER_NAME, img_size=S,
                     seed=args.seed, precision=ops.precision(), truncation=args.truncation, n_per_caption=K, best_of=args.best_of or None,
-                    captions=n, grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
+                    captions=n, fid=fid, grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

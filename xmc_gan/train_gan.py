@@ -36,7 +36,7 @@ from xmc_gan.model.concept_gan import InNetG as CONCEPT_INATTN_GEN, OutNetG as C
 from xmc_gan.model.encoder import RNN_ENCODER, SBERT_ENCODER
 from xmc_gan.utils.logger import setup_logger
 from xmc_gan.utils.miscc import count_params
-from xmc_gan.utils.visual import ScalarLog, fid_between, flush_saves, save_image, save_image_async, to_uint8_hwc
+from xmc_gan.utils.visual import ScalarLog, fid_between, fid_extractor, flush_saves, save_image, save_image_async, to_uint8_hwc
 from xmc_gan_amd import ops, parallel
 from xmc_gan_amd.augment import DiffAugment, parse_policy
 from xmc_gan_amd.optim import HipAdam, ParamEMA
@@ -78,6 +78,9 @@ def parse_args(argv=None):
                              'the per-epoch sample grid, eval() and netG_ema_<epoch>.pth use it.  0 (default): off')
     parser.add_argument('--ema_start', type=int, default=0,
                         help='generator steps before the averaging starts: until then the average is a copy of the weights')
+    parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
+                        help="FID Inception weights (the pt_inception-2015-12-05-*.pth state dict of pytorch_fid): eval() scores on this "
+                             "project's kernels (default: $XMC_FID_INCEPTION; without either, pytorch_fid if it is installed)")
     parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
                         help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (config.json, weights, tokenizer '
                              'files; default: $XMC_SBERT_DIR).  Without it the SBERT presets run with --synthetic only')
@@ -645,12 +648,35 @@ def _detached(last):
     return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in last.items()}
 
 
+_FID_INCEPTION = ['']        # --fid_inception (main()); eval() falls back to $XMC_FID_INCEPTION
+
+
+def _fid_u8(images_nchw, device):
+    """[B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] on the device: trunc((x + 1) * 127.5), the bytes eval() writes into the PNGs"""
+    from xmc_gan_amd.fid import nchw_to_u8
+    return nchw_to_u8(images_nchw.to(device))
+
+
+def _real_stats(loader, extractor, device, limit):
+    """statistics of the loader's real images alone (the cached ones were made for another number of samples)"""
+    from xmc_gan_amd.fid import FeatureStats
+    st = FeatureStats(device=device)
+    for imgs, _, _ in loader:
+        st.update(extractor(_fid_u8(imgs, device)))
+        if st.n >= limit:
+            break
+    return st
+
+
 @torch.no_grad()
-def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None):
+def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to
     ``save_dir/<key>.png`` and, unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``,
-    as 8-bit PNGs of (x + 1) * 127.5; FID between the two directories when ``pytorch_fid`` is importable (logged and written to
-    the scalar log as 'FID').  Returns (uint8 tensor of the generated images, FID or None)."""
+    as 8-bit PNGs of (x + 1) * 127.5.  FID (logged and written to the scalar log as 'FID'):
+    with ``fid_inception`` (default: --fid_inception, then $XMC_FID_INCEPTION) on this project's kernels -- the generated images go to the
+    extractor from the device as the bytes the PNGs hold, the real images' statistics are computed once and cached beside ``org_dir`` as
+    ``org_stats.npz`` (reused while its sample count matches); otherwise between the two directories when ``pytorch_fid`` is importable.
+    Returns (uint8 tensor of the generated images, FID or None)."""
     from PIL import Image
     netG.eval()
     device = next(netG.parameters()).device
@@ -660,6 +686,17 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     if org_dir:
         os.makedirs(org_dir, exist_ok=True)
         save_org = len(os.listdir(org_dir)) != num_samples
+    weights = fid_inception or _FID_INCEPTION[0] or os.environ.get('XMC_FID_INCEPTION', '')
+    extractor = gen_stats = real_stats = cached = cache = None
+    if weights:
+        from xmc_gan_amd.fid import FeatureStats, frechet_distance, load_stats
+        extractor = fid_extractor(weights, device)
+        gen_stats = FeatureStats(device=device)
+        cache = os.path.join(os.path.dirname(os.path.abspath(org_dir)), 'org_stats.npz') if org_dir else None
+        if cache and os.path.isfile(cache):
+            cached = load_stats(cache, with_count=True)
+        if cached is None:
+            real_stats = FeatureStats(device=device)
     cnt, outs = 0, []
     for imgs, texts_lst, keys in loader:
         caps, cap_lens = texts_lst[0]
@@ -667,6 +704,10 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
+        if extractor is not None:
+            gen_stats.update(extractor(_fid_u8(fake, device)))
+            if real_stats is not None:
+                real_stats.update(extractor(_fid_u8(imgs, device)))
         for j in range(fake.size(0)):
             if save_dir:
                 Image.fromarray(to_uint8_hwc(fake[j])).save(f'{save_dir}/{keys[j]}.png')
@@ -675,9 +716,22 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         cnt += fake.size(0)
         if cnt >= num_samples:
             break
-    fid = fid_between(org_dir, save_dir, device) if (save_dir and org_dir and cnt) else None
+    if extractor is not None:
+        fid, why = None, 'fewer than two images'
+        if cnt >= 2:
+            if cached is not None and cached[2] == cnt:
+                real = cached[:2]
+            else:
+                if real_stats is None:        # a cache for another number of samples
+                    real_stats = _real_stats(loader, extractor, device, cnt)
+                real = real_stats.finalize()
+                if cache:
+                    real_stats.save(cache)
+            fid = frechet_distance(*real, *gen_stats.finalize())
+    else:
+        fid, why = (fid_between(org_dir, save_dir, device) if (save_dir and org_dir and cnt) else None), 'pytorch_fid is not installed'
     if fid is None:
-        logger.info(f' epoch {state_epoch}, generated {cnt} images (FID not computed: pytorch_fid is not installed)')
+        logger.info(f' epoch {state_epoch}, generated {cnt} images (FID not computed: {why})')
     else:
         logger.info(f' epoch {state_epoch}, FID : {fid}')
         if writer is not None:
@@ -715,6 +769,9 @@ def main(argv=None):
         cfg.TRAIN.MAX_EPOCH = args.max_epoch
     if args.precision:
         ops.set_precision(args.precision)
+    _FID_INCEPTION[0] = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
+    if _FID_INCEPTION[0] and not os.path.isfile(_FID_INCEPTION[0]):
+        raise SystemExit(f'--fid_inception: {_FID_INCEPTION[0]} is not a file')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', str(args.gpu_id)))

@@ -4,8 +4,9 @@ The reference leans on three packages that are optional here (none is on the ste
 the sample grids, ``tensorboard`` / ``wandb`` for scalars, ``pytorch_fid`` for the FID of the generated test set.  The grid
 writer below restates what the reference's call ``save_image(x, path, normalize=True, scale_each=True)`` produces (eight images
 per row, two pixels of padding, every image min-max scaled on its own) on PIL + numpy; the scalar log uses whichever backend is
-importable and always keeps a JSON-lines copy next to it; FID is computed when ``pytorch_fid`` can be imported and reported as
-unavailable otherwise."""
+importable and always keeps a JSON-lines copy next to it; FID is computed on this project's own kernels when the FID Inception
+weights are given (``fid_between(weights=)``, xmc_gan_amd.fid), else when ``pytorch_fid`` can be imported, and reported as unavailable
+otherwise."""
 import json
 import math
 import os
@@ -216,8 +217,27 @@ class ScalarLog:
             self._f.close()
 
 
-def fid_between(dir_a, dir_b, device, batch_size=100, dims=2048):
-    """calculate_fid_given_paths([org_dir, save_dir], ...) (train_gan.py:389) when pytorch_fid imports; None otherwise."""
+_fid_extractors = {}
+
+
+def fid_extractor(weights, device):
+    """the native Inception feature extractor of ``weights`` on ``device`` (xmc_gan_amd.fid.InceptionFID), built once per file and device"""
+    import torch
+    from xmc_gan_amd.fid import InceptionFID
+    key = (os.path.abspath(weights), str(torch.device(device)))
+    if key not in _fid_extractors:
+        _fid_extractors[key] = InceptionFID(weights, device)
+    return _fid_extractors[key]
+
+
+def fid_between(dir_a, dir_b, device, batch_size=100, dims=2048, weights=None):
+    """calculate_fid_given_paths([org_dir, save_dir], ...) (train_gan.py:389).  ``weights`` (the FID Inception state dict): scored on this
+    project's kernels (xmc_gan_amd.fid; each side an image directory or an .npz statistics file).  Without it: pytorch_fid when it
+    imports; None otherwise."""
+    if weights:
+        from xmc_gan_amd.fid import frechet_distance, stats_of
+        ex = fid_extractor(weights, device)
+        return frechet_distance(*stats_of(dir_a, ex, batch_size), *stats_of(dir_b, ex, batch_size))
     try:
         from pytorch_fid.fid_score import calculate_fid_given_paths
     except Exception:       # noqa: BLE001 -- optional third-party package (and its pretrained Inception weights)
