@@ -49,7 +49,8 @@ extern "C" {
  *     Added without a new version (additions only): xmc_diffaug_sums / xmc_diffaug_apply (csrc/augment.hip);
  *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip);
  *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip);
- *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip). */
+ *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip);
+ *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -717,10 +718,27 @@ int xmc_fid_resize_u8(const uint8_t* src, float* dst, int N, int H, int W, int O
  * (floor; H, W >= 3 or XMC_ESHAPE).  XMC_POOL_AVG_VALID divides by the number of in-image pixels of the window (count_include_pad=False). */
 #define XMC_POOL_MAX 0
 #define XMC_POOL_AVG_VALID 1
+/* XMC_POOL_AVG_PAD: sum of the in-image pixels of the window / 9 (count_include_pad=True: torchvision's branch_pool); stride 1 only, stride 2
+ * with this mode is XMC_EINVAL. */
+#define XMC_POOL_AVG_PAD 2
 int xmc_pool3x3(const float* x, float* y, int N, int H, int W, int C, int mode, int stride, void* stream);
+/* resize_bilinear_f32: src f32 NCHW [N,3,H,W] (what a generator returns) -> dst f32 engine image [N,OH,OW,8] by resize_u8's coordinate rule
+ * (source coordinate in f64, blend in f32); the values are not rescaled; channels 3..7 = 0.  OH == H and OW == W copies the values exactly.
+ * Shapes and alignment as resize_u8. */
+int xmc_resize_bilinear_f32(const float* src, float* dst, int N, int H, int W, int OH, int OW, void* stream);
 /* moments: sum f64 [D] += column sums of x f32 [B,D]; outer f64 [D,D] += x^T x (products and sums in f64).  The caller zeroes both before
  * the first batch.  One owner thread per output element, batch rows added in order: no atomics, bit-identical from run to run. D <= 32768. */
 int xmc_fid_moments(const float* x, double* sum, double* outer, int B, int D, void* stream);
+
+/* ---- R-precision: caption retrieval among K candidates per image (csrc/retrieval.hip; xmc_gan_amd/rprecision.py) ---------------------------
+ * img f32 [N,D] image codes, txt f32 [M,D] caption codes, cand int32 [N,K] rows of txt (column 0: the image's own caption; every entry in
+ * [0, M): the CALLER checks that, the kernel does not).  score[n][k] = dot(img[n], txt[c]) / max(|img[n]| * |txt[c]|, 1e-8), c = cand[n][k]
+ * (AttnGAN's cosine and its clamp); rank[n] = #{k >= 1 : score[n][k] > score[n][0]} (strict: argmax gives a tie to index 0), K when
+ * score[n][0] is NaN.  R-precision hit: rank == 0.  `score` f32 [N,K] may be NULL.  One wave per image, the [N,K,D] gather is never
+ * materialised, fixed-order reductions, no atomics: bit-identical from run to run.
+ * XMC_EINVAL: img / txt / cand / rank NULL or N, M, K < 1; XMC_ESHAPE: D % 4 != 0, D < 4 or D > 1024; XMC_EALIGN: img / txt not 16-byte
+ * aligned.  All refused before any launch. */
+int xmc_rprecision(const float* img, const float* txt, const int32_t* cand, int32_t* rank, float* score, int N, int M, int K, int D, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,9 +6,11 @@
 //               then 2 * (v / 255) - 1; channels 3..7 are zero.  The source coordinate is worked out in f64 (one per row and column of a
 //               thread's pixel), the blend in f32 on the byte values: with OH == H and OW == W both weights are exactly 1 and 0 and the
 //               result EQUALS 2 * (b / 255) - 1.
+//   resize_f32  f32 NCHW [N,3,H,W] (what a generator returns) -> the same engine image by the same coordinate rule, values not rescaled: the
+//               front end of the DAMSM image encoder (xmc_gan/model/encoder.py CNN_ENCODER).  Equal sizes: weights 1 and 0, the input exactly.
 //   pool3x3     3x3 max pool / average over the in-image pixels of the window (count_include_pad=False) on f32 [N,H,W,C], C % 4 == 0:
 //               stride 1 with padding 1 (OH = H) or stride 2 without padding (OH = (H - 3) / 2 + 1, floor).  One thread per output pixel and
-//               16-byte channel unit.
+//               16-byte channel unit.  Mode 2 (stride 1 only) divides the same sum by 9 (count_include_pad=True: torchvision's branch_pool).
 //   moments     running f64 statistics of a batch of f32 feature rows X [B,D]: sum[d] += sum_b X[b][d], outer[i][j] += sum_b X[b][i] X[b][j],
 //               products and sums in f64.  Every output element has ONE owner thread that adds its batch rows in order: no atomics, the same
 //               bytes for the same batches every time.  64 x 64 tiles of `outer`, 4 x 4 elements per thread, the two 64-column strips of X
@@ -57,7 +59,32 @@ __global__ void __launch_bounds__(NT) fid_resize_u8_kernel(const uint8_t* __rest
     }
 }
 
-// MODE 0: max, 1: sum / number of in-image pixels.  STRIDE 1 (padding 1) or 2 (no padding).
+__global__ void __launch_bounds__(NT) resize_bilinear_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int H, int W, int OH,
+                                                                int OW) {
+    const int64_t P = (int64_t)N * OH * OW;
+    const size_t plane = (size_t)H * W;
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < P; p += (int64_t)gridDim.x * NT) {
+        const int ox = (int)(p % OW);
+        const int64_t q = p / OW;
+        const int oy = (int)(q % OH), n = (int)(q / OH);
+        const Lerp ly = src_coord(oy, H, OH), lx = src_coord(ox, W, OW);
+        const float* img = src + (size_t)n * 3 * plane;
+        const size_t o00 = (size_t)ly.i0 * W + lx.i0, o01 = (size_t)ly.i0 * W + lx.i1, o10 = (size_t)ly.i1 * W + lx.i0, o11 = (size_t)ly.i1 * W + lx.i1;
+        const float wx1 = lx.l, wx0 = 1.f - lx.l, wy1 = ly.l, wy0 = 1.f - ly.l;
+        f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* pl = img + (size_t)c * plane;
+            const float top = wx0 * pl[o00] + wx1 * pl[o01];
+            const float bot = wx0 * pl[o10] + wx1 * pl[o11];
+            lo[c] = wy0 * top + wy1 * bot;
+        }
+        f32x4* o = reinterpret_cast<f32x4*>(dst) + (size_t)p * 2;
+        o[0] = lo; o[1] = hi;
+    }
+}
+
+// MODE 0: max, 1: sum / number of in-image pixels, 2: sum / 9.  STRIDE 1 (padding 1) or 2 (no padding).
 template <int MODE, int STRIDE>
 __global__ void __launch_bounds__(NT) pool3x3_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C4, int OH, int OW) {
     const int64_t items = (int64_t)N * OH * OW * C4;
@@ -94,6 +121,10 @@ __global__ void __launch_bounds__(NT) pool3x3_kernel(const float* __restrict__ x
             const float inv = (float)cnt;
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = acc[k] / inv;
+        }
+        if (MODE == 2) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = acc[k] / 9.f;
         }
         y4[t] = acc;
     }
@@ -168,8 +199,21 @@ extern "C" int xmc_fid_resize_u8(const uint8_t* src, float* dst, int N, int H, i
     return 0;
 }
 
+extern "C" int xmc_resize_bilinear_f32(const float* src, float* dst, int N, int H, int W, int OH, int OW, void* stream) {
+    if (!src || !dst) return XMC_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return XMC_ESHAPE;
+    if ((int64_t)H * W > (int64_t)1 << 30 || (int64_t)OH * OW > (int64_t)1 << 30) return XMC_ESHAPE;
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) || (reinterpret_cast<uintptr_t>(src) & 3)) return XMC_EALIGN;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(resize_bilinear_f32_kernel, dim3(blocks_for((int64_t)N * OH * OW, 16384)), dim3(NT), 0, st, src, dst, N, H, W, OH, OW);
+    xmc_note_kernel("resize_bilinear_f32_kernel");
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int xmc_pool3x3(const float* x, float* y, int N, int H, int W, int C, int mode, int stride, void* stream) {
-    if (!x || !y || (mode != XMC_POOL_MAX && mode != XMC_POOL_AVG_VALID) || (stride != 1 && stride != 2)) return XMC_EINVAL;
+    if (!x || !y || (mode != XMC_POOL_MAX && mode != XMC_POOL_AVG_VALID && mode != XMC_POOL_AVG_PAD) || (stride != 1 && stride != 2)) return XMC_EINVAL;
+    if (mode == XMC_POOL_AVG_PAD && stride != 1) return XMC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || C < 4) return XMC_ESHAPE;
     if (stride == 2 && (H < 3 || W < 3)) return XMC_ESHAPE;               // no whole window: the output would be empty
     if (C % 4 != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15)) return XMC_EALIGN;
@@ -178,7 +222,8 @@ extern "C" int xmc_pool3x3(const float* x, float* y, int N, int H, int W, int C,
     const dim3 grid(blocks_for((int64_t)N * OH * OW * (C / 4), 1 << 20)), block(NT);
 #define XMC_POOL_GO(M_, S_) hipLaunchKernelGGL((pool3x3_kernel<M_, S_>), grid, block, 0, st, x, y, N, H, W, C / 4, OH, OW)
     if (mode == XMC_POOL_MAX) { if (stride == 1) XMC_POOL_GO(0, 1); else XMC_POOL_GO(0, 2); }
-    else { if (stride == 1) XMC_POOL_GO(1, 1); else XMC_POOL_GO(1, 2); }
+    else if (mode == XMC_POOL_AVG_VALID) { if (stride == 1) XMC_POOL_GO(1, 1); else XMC_POOL_GO(1, 2); }
+    else XMC_POOL_GO(2, 1);
 #undef XMC_POOL_GO
     xmc_note_kernel("pool3x3_kernel<%d, %d>", mode, stride);
     XMC_LAUNCH_CHECK();

@@ -5,7 +5,8 @@
 ``ops.set_precision`` says: the 94 convolutions (BatchNorm folded in, ReLU in the epilogue) through ``xmc_conv_igemm``'s tap tables, the
 image front end, the 3x3 pools and the f64 feature moments through csrc/fid.hip.  The weights are a file the user supplies
 (``weights=`` / ``XMC_FID_INCEPTION``): the ``pt_inception-2015-12-05-*.pth`` state dict of pytorch_fid, torchvision key names.
-``FeatureStats`` accumulates mean and covariance on the device in f64; ``frechet_distance`` is host f64 numpy (two symmetric
+The layers, blocks and trunk live in ``InceptionTrunk``, which also runs torchvision's flavour of the network (``variant="torchvision"``:
+the trunk of the DAMSM image encoder, xmc_gan_amd/rprecision.py).  ``FeatureStats`` accumulates mean and covariance on the device in f64; ``frechet_distance`` is host f64 numpy (two symmetric
 eigendecompositions and one SVD, no scipy).  Statistics files are pytorch_fid's ``.npz`` (``mu``, ``sigma``).
 
 Agreement with pytorch_fid on the real weights file has not been checked (neither is available where this was written); what is checked is
@@ -91,6 +92,23 @@ def fold_bn(w, gamma, beta, mean, var, eps=BN_EPS):
     return (w * scale[:, None, None, None]).float().contiguous(), (beta - mean * scale).float().contiguous()
 
 
+def check_inception_state(sd, who, where):
+    """{layer: (weight, gamma, beta, running_mean, running_var)} of a state dict with torchvision's Inception-v3 key names, checked against
+    `inception_layers()`.  ImportError: a missing key; ValueError: a wrong shape.  Other keys are ignored."""
+    out = {}
+    for name, (cin, cout, (kh, kw), _, _) in inception_layers().items():
+        keys = [(f"{name}.conv.weight", (cout, cin, kh, kw))] + [(f"{name}.bn.{k}", (cout,)) for k in ("weight", "bias", "running_mean", "running_var")]
+        got = []
+        for key, shape in keys:
+            if key not in sd:
+                raise ImportError(f"{who}: the weights in {where} lack {key!r}")
+            if tuple(sd[key].shape) != shape:
+                raise ValueError(f"{who}: {key} is {tuple(sd[key].shape)}, Inception-v3 has {shape}")
+            got.append(sd[key])
+        out[name] = tuple(got)
+    return out
+
+
 def load_inception_weights(path=None):
     """The FID Inception state dict of ``path`` (default: $XMC_FID_INCEPTION), checked against `inception_layers()`: {layer: (weight,
     gamma, beta, running_mean, running_var)}.  ``fc.*`` and ``num_batches_tracked`` are ignored.  ImportError: no path, no file, a
@@ -105,18 +123,7 @@ def load_inception_weights(path=None):
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if not isinstance(sd, dict):
         raise ImportError(f"InceptionFID: {path} holds a {type(sd).__name__}, a state dict was expected")
-    out = {}
-    for name, (cin, cout, (kh, kw), _, _) in inception_layers().items():
-        keys = [(f"{name}.conv.weight", (cout, cin, kh, kw))] + [(f"{name}.bn.{k}", (cout,)) for k in ("weight", "bias", "running_mean", "running_var")]
-        got = []
-        for key, shape in keys:
-            if key not in sd:
-                raise ImportError(f"InceptionFID: the weights in {path} lack {key!r}")
-            if tuple(sd[key].shape) != shape:
-                raise ValueError(f"InceptionFID: {key} is {tuple(sd[key].shape)}, Inception-v3 has {shape}")
-            got.append(sd[key])
-        out[name] = tuple(got)
-    return out
+    return check_inception_state(sd, "InceptionFID", path)
 
 
 def conv_bias_relu(x, w, b, geom):
@@ -132,14 +139,20 @@ def conv_bias_relu(x, w, b, geom):
     return out
 
 
-class InceptionFID:
-    """uint8 images [N,H,W,3] on the device -> pool3 features f32 [N,2048].  ``resize_to``: the side the front end resizes to (299, as
-    pytorch_fid does; None: the images go in at their own size, which must be at least 75x75).  Frozen: nothing here is differentiable."""
+VARIANTS = ("fid", "torchvision")
 
-    def __init__(self, weights=None, device="cuda", resize_to=299):
-        raw = load_inception_weights(weights)
+
+class InceptionTrunk:
+    """The 94 folded convolutions of Inception-v3 and its blocks, on f32 engine tensors [N,H,W,C].  ``raw``: what `load_inception_weights`
+    returns.  ``variant`` "fid": pytorch_fid's network (pool branches average over the in-image pixels, Mixed_7c's is a max pool);
+    "torchvision": every ``branch_pool`` is avg_pool2d(3, 1, 1) with its default count_include_pad=True -- the sum / 9 -- Mixed_7c's
+    included (the network AttnGAN's DAMSM image encoder was trained on: xmc_gan/model/encoder.py CNN_ENCODER)."""
+
+    def __init__(self, raw, device="cuda", variant="fid"):
+        if variant not in VARIANTS:
+            raise ValueError(f"InceptionTrunk: variant {variant!r}, one of {VARIANTS} expected")
         self.device = torch.device(device)
-        self.resize_to = resize_to
+        self.variant = variant
         self.layers = {}
         for name, (cin, cout, k, s, p) in inception_layers().items():
             w, b = fold_bn(*raw[name])
@@ -160,29 +173,31 @@ class InceptionFID:
     def block(self, name, x):
         """one Mixed_* block on f32 [N,H,W,BLOCK_IN[name]]"""
         ch = lambda *names: self.chain(name, names, x)      # noqa: E731
+        avg = "avg" if self.variant == "fid" else "avg_pad"
         if name in ("Mixed_5b", "Mixed_5c", "Mixed_5d"):
             outs = [ch("branch1x1"), ch("branch5x5_1", "branch5x5_2"), ch("branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3"),
-                    self.conv(name + ".branch_pool", ops.pool3x3(x, "avg", 1))]
+                    self.conv(name + ".branch_pool", ops.pool3x3(x, avg, 1))]
         elif name == "Mixed_6a":
             outs = [ch("branch3x3"), ch("branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3"), ops.pool3x3(x, "max", 2)]
         elif name in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
             outs = [ch("branch1x1"), ch("branch7x7_1", "branch7x7_2", "branch7x7_3"),
                     ch("branch7x7dbl_1", "branch7x7dbl_2", "branch7x7dbl_3", "branch7x7dbl_4", "branch7x7dbl_5"),
-                    self.conv(name + ".branch_pool", ops.pool3x3(x, "avg", 1))]
+                    self.conv(name + ".branch_pool", ops.pool3x3(x, avg, 1))]
         elif name == "Mixed_7a":
             outs = [ch("branch3x3_1", "branch3x3_2"), ch("branch7x7x3_1", "branch7x7x3_2", "branch7x7x3_3", "branch7x7x3_4"),
                     ops.pool3x3(x, "max", 2)]
         elif name in ("Mixed_7b", "Mixed_7c"):
             b3, bd = ch("branch3x3_1"), ch("branch3x3dbl_1", "branch3x3dbl_2")
+            pool = "max" if (name == "Mixed_7c" and self.variant == "fid") else avg                        # (7c: pytorch_fid's max pool)
             outs = [ch("branch1x1"), self.conv(name + ".branch3x3_2a", b3), self.conv(name + ".branch3x3_2b", b3),
                     self.conv(name + ".branch3x3dbl_3a", bd), self.conv(name + ".branch3x3dbl_3b", bd),
-                    self.conv(name + ".branch_pool", ops.pool3x3(x, "avg" if name == "Mixed_7b" else "max", 1))]      # (7c: pytorch_fid's max pool)
+                    self.conv(name + ".branch_pool", ops.pool3x3(x, pool, 1))]
         else:
             raise KeyError(name)
         return torch.cat(outs, dim=3)
 
-    def trunk(self, x8):
-        """f32 engine image [N,H,W,8] in [-1, 1] -> features f32 [N,2048]"""
+    def trunk(self, x8, with_mixed_6e=False):
+        """f32 engine image [N,H,W,8] in [-1, 1] -> features f32 [N,2048]; ``with_mixed_6e``: (Mixed_6e's output [N,h,w,768], features)"""
         x = self.conv("Conv2d_1a_3x3", x8)
         x = self.conv("Conv2d_2a_3x3", x)
         x = self.conv("Conv2d_2b_3x3", x)
@@ -190,12 +205,24 @@ class InceptionFID:
         x = self.conv("Conv2d_3b_1x1", x)
         x = self.conv("Conv2d_4a_3x3", x)
         x = ops.pool3x3(x, "max", 2)
+        mid = None
         for name in BLOCKS:
             x = self.block(name, x)
+            if name == "Mixed_6e":
+                mid = x
         N, H, W, Cc = x.shape
         y = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
         L.call("xmc_global_avgpool", ops._p(x), ops._p(y), N, H * W, Cc, L.F32, L.F32, ops._st())
-        return y
+        return (mid, y) if with_mixed_6e else y
+
+
+class InceptionFID(InceptionTrunk):
+    """uint8 images [N,H,W,3] on the device -> pool3 features f32 [N,2048].  ``resize_to``: the side the front end resizes to (299, as
+    pytorch_fid does; None: the images go in at their own size, which must be at least 75x75).  Frozen: nothing here is differentiable."""
+
+    def __init__(self, weights=None, device="cuda", resize_to=299):
+        super().__init__(load_inception_weights(weights), device, "fid")
+        self.resize_to = resize_to
 
     @torch.no_grad()
     def __call__(self, u8):

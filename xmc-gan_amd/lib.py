@@ -17,7 +17,7 @@ BF16, F32 = 0, 1
 H16 = BF16
 ACT_NONE, ACT_LRELU, ACT_TANH, ACT_RELU = 0, 1, 2, 3
 MAX_TAPS, MAX_CLASSES = 16, 4
-POOL_MAX, POOL_AVG_VALID = 0, 1     # xmc_pool3x3 modes
+POOL_MAX, POOL_AVG_VALID, POOL_AVG_PAD = 0, 1, 2     # xmc_pool3x3 modes
 DIFFAUG_PARTS = 64        # XMC_DIFFAUG_PARTS: partials per image of xmc_diffaug_sums and xmc_image_minmax
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -179,6 +179,8 @@ _SIGS = {
     "xmc_fid_resize_u8": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_pool3x3": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "xmc_fid_moments": [vp, vp, vp, i32, i32, vp],
+    "xmc_resize_bilinear_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "xmc_rprecision": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
 }
 _RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p}
 EXPORTS = tuple(_SIGS)

@@ -363,18 +363,37 @@ def fid_resize_u8(u8, out_hw=None):
     return y
 
 
+_POOL_MODES = {"max": L.POOL_MAX, "avg": L.POOL_AVG_VALID, "avg_pad": L.POOL_AVG_PAD}
+
+
+def resize_bilinear_f32(x, out_hw=None):
+    """f32 NCHW [N,3,H,W] (what a generator returns) -> f32 engine image [N,OH,OW,8]: bilinear (align_corners=False, no antialias) to
+    ``out_hw`` (None: the size it has) by `fid_resize_u8`'s coordinate rule, values not rescaled; channels 3..7 are zero"""
+    x = _fid_arg(x, "resize_bilinear_f32", torch.float32, 4)
+    N, c, H, W = x.shape
+    if c != 3 or N < 1 or H < 1 or W < 1:
+        raise ValueError(f"resize_bilinear_f32: f32 [N,3,H,W] expected, got {tuple(x.shape)}")
+    OH, OW = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if OH < 1 or OW < 1:
+        raise ValueError(f"resize_bilinear_f32: output size {OH}x{OW}")
+    y = torch.empty((N, OH, OW, 8), dtype=torch.float32, device=x.device)
+    L.call("xmc_resize_bilinear_f32", _p(x), _p(y), N, H, W, OH, OW, _st())
+    return y
+
+
 def pool3x3(x, mode, stride):
-    """3x3 pool of f32 [N,H,W,C] (C % 4 == 0).  ``mode`` 'max' or 'avg' (the sum over the window's in-image pixels divided by their number:
-    avg_pool2d(count_include_pad=False)); ``stride`` 1 (padding 1, same size) or 2 (no padding, floor((H - 3) / 2) + 1 rows)"""
+    """3x3 pool of f32 [N,H,W,C] (C % 4 == 0).  ``mode`` 'max', 'avg' (the sum over the window's in-image pixels divided by their number:
+    avg_pool2d(count_include_pad=False)) or 'avg_pad' (the same sum / 9: count_include_pad=True; stride 1 only); ``stride`` 1 (padding 1,
+    same size) or 2 (no padding, floor((H - 3) / 2) + 1 rows)"""
     x = _fid_arg(x, "pool3x3", torch.float32, 4)
-    if mode not in ("max", "avg") or stride not in (1, 2):
+    if mode not in _POOL_MODES or stride not in (1, 2) or (mode == "avg_pad" and stride != 1):
         raise ValueError(f"pool3x3: mode {mode!r}, stride {stride}")
     N, H, W, Cc = x.shape
     if N < 1 or Cc < 4 or Cc % 4 or H < 1 or W < 1 or (stride == 2 and (H < 3 or W < 3)):
         raise ValueError(f"pool3x3: {tuple(x.shape)} at stride {stride} (C % 4 == 0; stride 2 needs a whole 3x3 window)")
     OH, OW = (H, W) if stride == 1 else ((H - 3) // 2 + 1, (W - 3) // 2 + 1)
     y = torch.empty((N, OH, OW, Cc), dtype=torch.float32, device=x.device)
-    L.call("xmc_pool3x3", _p(x), _p(y), N, H, W, Cc, L.POOL_MAX if mode == "max" else L.POOL_AVG_VALID, stride, _st())
+    L.call("xmc_pool3x3", _p(x), _p(y), N, H, W, Cc, _POOL_MODES[mode], stride, _st())
     return y
 
 
@@ -389,6 +408,31 @@ def fid_moments(feats, total, outer):
     if B < 1:
         raise ValueError("fid_moments: an empty batch")
     L.call("xmc_fid_moments", _p(feats), _p(total), _p(outer), B, D, _st())
+
+
+# ------------------------------------------------------------------------------------------ R-precision (csrc/retrieval.hip): f32, outside autograd
+def rprecision(img, txt, cand, return_scores=False):
+    """Caption retrieval among K candidates per image: img f32 [N,D] image codes, txt f32 [M,D] caption codes, cand int32 [N,K] rows of
+    ``txt`` (column 0: the image's own caption) -> rank int32 [N], the number of other candidates whose cosine beats the own caption's
+    (0: a hit; K: the own caption scored NaN); ``return_scores``: (rank, score f32 [N,K]).  D % 4 == 0, D <= 1024.  ``cand`` is checked
+    against [0, M) here, on the host (one synchronising reduction when it lives on the device)."""
+    img, txt = _fid_arg(img, "rprecision", torch.float32, 2), _fid_arg(txt, "rprecision", torch.float32, 2)
+    cand = torch.as_tensor(cand)
+    if cand.dim() != 2 or cand.dtype != torch.int32:
+        raise ValueError(f"rprecision: cand int32 [N,K] expected, got {cand.dtype} {tuple(cand.shape)}")
+    (N, D), (M, D2), K = img.shape, txt.shape, cand.shape[1]
+    if D != D2 or cand.shape[0] != N or N < 1 or M < 1 or K < 1 or txt.device != img.device:
+        raise ValueError(f"rprecision: img {tuple(img.shape)}, txt {tuple(txt.shape)}, cand {tuple(cand.shape)} do not fit")
+    if D % 4 or D > 1024:
+        raise ValueError(f"rprecision: D = {D}; D % 4 == 0 and D <= 1024 expected")
+    lo, hi = int(cand.min()), int(cand.max())
+    if lo < 0 or hi >= M:
+        raise ValueError(f"rprecision: candidate indices span [{lo}, {hi}], txt has {M} rows")
+    cand = cand.to(img.device).contiguous()
+    rank = torch.empty((N,), dtype=torch.int32, device=img.device)
+    score = torch.empty((N, K), dtype=torch.float32, device=img.device) if return_scores else None
+    L.call("xmc_rprecision", _p(img), _p(txt), _p(cand), _p(rank), _p(score), N, M, K, D, _st())
+    return (rank, score) if return_scores else rank
 
 
 # ------------------------------------------------------------------------------------------ differentiable augmentation

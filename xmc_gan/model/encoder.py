@@ -1,4 +1,5 @@
-"""Frozen text encoders with the reference's class names and call signature (model/encoder.py).
+"""Frozen encoders: the reference's two text encoders with its class names and call signature (model/encoder.py), and the image half
+of the DAMSM pair, which the reference does not have (``CNN_ENCODER``, AttnGAN's, for R-precision).
 
 ``RNN_ENCODER`` (the DAMSM caption encoder, encoder.py:73-153) holds an ``nn.Embedding`` and an ``nn.LSTM`` as parameter
 containers -- ``state_dict()`` keys and shapes are upstream's, so ``text_encoder100.pth`` loads unchanged -- and runs
@@ -12,6 +13,10 @@ the user supplies (``model_dir`` / ``XMC_SBERT_DIR``: config.json, weights, toke
 runs the forward on the MI355X: four MFMA GEMMs per layer through ``ops.linear`` and the kernels of csrc/transformer.hip
 (embedding sum + LayerNorm, fused short-sequence attention, bias + erf GELU, residual + LayerNorm, the pooling tail).
 Without a model directory constructing it fails loudly (ImportError), as before.
+
+``CNN_ENCODER`` (AttnGAN model.py, not in the reference) is torchvision's Inception-v3 up to ``Mixed_7c`` plus two projections, with
+AttnGAN's ``state_dict()`` keys so that ``image_encoder100.pth`` loads unchanged.  Its forward is the f32 Inception trunk of
+``xmc_gan_amd.fid`` in its torchvision variant, behind a float (or uint8) bilinear front end.
 """
 import json
 import os
@@ -19,6 +24,8 @@ import os
 import torch
 import torch.nn as nn
 
+from xmc_gan_amd import fid as _fid
+from xmc_gan_amd import lib as _L
 from xmc_gan_amd import ops
 
 
@@ -315,3 +322,107 @@ class SBERT_ENCODER(nn.Module):
         ids, lens = self.tokenize(sents)
         T = int(lens.max())
         return self.forward_ids(ids[:, :T], lens)
+
+
+class _BasicConv2d(nn.Module):
+    """torchvision's BasicConv2d as a parameter container: conv without bias, BatchNorm with eps 1e-3"""
+
+    def __init__(self, cin, cout, k, s, p):
+        super(_BasicConv2d, self).__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel_size=k, stride=s, padding=p, bias=False)
+        self.bn = nn.BatchNorm2d(cout, eps=_fid.BN_EPS)
+
+
+class CNN_ENCODER(nn.Module):
+    """``CNN_ENCODER(nef)``: AttnGAN's image encoder (model.py CNN_ENCODER).  ``forward(x)``: f32 [B,3,H,W] in [-1, 1] ->
+    ``features [B,nef,17,17]`` (``emb_features`` of Mixed_6e's output), ``cnn_code [B,nef]`` (``emb_cnn_code`` of the pooled Mixed_7c
+    output), both f32.  ``encode_u8``: the same from uint8 [N,H,W,3].  The 94 BasicConv2d modules and the two projections hold upstream's
+    parameters and buffers (no ``fc``, no ``AuxLogits``: AttnGAN's checkpoint has neither); the forward runs on f64-folded f32 copies of
+    them through the HIP kernels, in f32 whatever ``ops.set_precision`` says.  Frozen, evaluation mode only.
+    ``resize_to``: 299 as upstream; None feeds the images at their own size (at least 75x75; the tests' small maps)."""
+
+    def __init__(self, nef, resize_to=299):
+        super(CNN_ENCODER, self).__init__()
+        self.nef = int(nef)
+        self.resize_to = resize_to
+        for name, (cin, cout, k, s, p) in _fid.inception_layers().items():
+            parent = self
+            *path, leaf = name.split(".")
+            for part in path:
+                if not hasattr(parent, part):
+                    parent.add_module(part, nn.Module())
+                parent = getattr(parent, part)
+            parent.add_module(leaf, _BasicConv2d(cin, cout, k, s, p))
+        self.emb_features = nn.Conv2d(768, self.nef, kernel_size=1, stride=1, padding=0, bias=False)      # AttnGAN's conv1x1
+        self.emb_cnn_code = nn.Linear(2048, self.nef)
+        initrange = 0.1                                                                                   # AttnGAN's init_trainable_weights
+        self.emb_features.weight.data.uniform_(-initrange, initrange)
+        self.emb_cnn_code.weight.data.uniform_(-initrange, initrange)
+        for p_ in self.parameters():
+            p_.requires_grad_(False)
+        self._folded = None
+        super(CNN_ENCODER, self).train(False)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("CNN_ENCODER runs frozen in eval mode (the DAMSM image encoder is an evaluation network here); "
+                                      "training it is not built")
+        return super(CNN_ENCODER, self).train(False)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        """upstream's checkpoints as they are, also with the ``module.`` prefix a DataParallel wrapper leaves on every key"""
+        if len(state_dict) and all(k.startswith("module.") for k in state_dict):
+            state_dict = {k[len("module."):]: v for k, v in state_dict.items()}
+        out = super(CNN_ENCODER, self).load_state_dict(state_dict, strict=strict, **kwargs)
+        self._folded = None
+        return out
+
+    def _net(self):
+        """(the folded trunk, emb_features as (geom, w, None), emb_cnn_code as (geom, w, b)) on the parameters' device; rebuilt when a
+        parameter or buffer changes (load_state_dict, .to())"""
+        sd = {k: v for k, v in self.state_dict(keep_vars=True).items() if v.is_floating_point()}
+        key = tuple((v.data_ptr(), v._version) for v in sd.values())
+        if self._folded is None or self._folded[0] != key:
+            dev = self.emb_cnn_code.weight.device
+            trunk = _fid.InceptionTrunk(_fid.check_inception_state(sd, "CNN_ENCODER", "the module"), dev, "torchvision")
+            frozen = lambda t: nn.Parameter(t.detach().to(dev, torch.float32).contiguous(), requires_grad=False)      # noqa: E731
+            cp = ops.pad_to(self.nef, 8)
+            bias = torch.zeros(cp, dtype=torch.float32, device=dev)
+            bias[:self.nef] = self.emb_cnn_code.bias.detach().float()
+            feat = (ops.ConvGeom(768, self.nef, 1, 1, 0), frozen(self.emb_features.weight), None)
+            code = (ops.ConvGeom(2048, self.nef, 1, 1, 0), frozen(self.emb_cnn_code.weight), bias)
+            self._folded = (key, trunk, feat, code)
+        return self._folded[1:]
+
+    def _encode(self, x8):
+        trunk, (gf, wf, _), (gc, wc, bc) = self._net()
+        mid, pooled = trunk.trunk(x8, with_mixed_6e=True)
+        f32 = torch.float32
+        feats = ops._conv_fwd_raw(mid, wf, None, gf, _L.ACT_NONE, f32)[..., :self.nef]                        # [B,h,w,nef]
+        code = ops._conv_fwd_raw(pooled.view(pooled.shape[0], 1, 1, 2048), wc, bc, gc, _L.ACT_NONE, f32)
+        return feats.permute(0, 3, 1, 2).contiguous(), code.view(pooled.shape[0], -1)[:, :self.nef].contiguous()
+
+    def _side(self, hw):
+        side = None if self.resize_to is None else (self.resize_to, self.resize_to)
+        if min(side or hw) < 75:
+            raise ValueError(f"CNN_ENCODER: Inception-v3 needs at least 75x75 pixels, got {tuple(side or hw)}")
+        return side
+
+    @torch.no_grad()
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("CNN_ENCODER runs frozen in eval mode")
+        x = torch.as_tensor(x)
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise ValueError(f"CNN_ENCODER: f32 images [B,3,H,W] in [-1, 1] expected, got {x.dtype} {tuple(x.shape)}")
+        x = x.detach().to(self.emb_cnn_code.weight.device)
+        return self._encode(ops.resize_bilinear_f32(x, self._side(x.shape[2:4])))
+
+    @torch.no_grad()
+    def encode_u8(self, u8):
+        """uint8 [N,H,W,3] (what `xmc_gan_amd.fid.nchw_to_u8` makes and PIL reads) -> the same pair, from 2 * (b / 255) - 1"""
+        u8 = torch.as_tensor(u8)
+        if u8.dim() != 4 or u8.shape[-1] != 3 or u8.dtype != torch.uint8:
+            raise ValueError(f"CNN_ENCODER: uint8 images [N,H,W,3] expected, got {u8.dtype} {tuple(u8.shape)}")
+        u8 = u8.to(self.emb_cnn_code.weight.device)
+        return self._encode(ops.fid_resize_u8(u8, self._side(u8.shape[1:3])))

@@ -3,6 +3,7 @@
     python xmc_gan/sample.py --cfg xmc_gan/cfg/<preset>.yml --checkpoint <netG_*.pth | netG_ema_*.pth> --out DIR
                              (--captions FILE | --token_ids FILE.npy | --synthetic N) [--n_per_caption K --seed S --truncation PSI]
                              [--best_of M --netD netD_*.pth] [--walk N] [--interp_sent N] [--grid_max N] [--no_png]
+                             [--fid_against DIR_OR_NPZ --fid_inception PATH] [--rprecision --damsm_image_encoder PATH]
 
 Writes ``<out>/<caption index:05d>_<k>.png`` (K images per caption), ``<out>/grid.png`` (the first ``--grid_max`` of them, every image min-max scaled
 on its own like the trainer's sample grids), ``<out>/captions.txt`` and ``<out>/manifest.json``.  The generator runs on the HIP kernels of
@@ -60,6 +61,12 @@ def parse_args(argv=None):
                         help='score the sampled images: FID against an image directory or an .npz statistics file -> manifest "fid"')
     parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
                         help='FID Inception weights for --fid_against (the pt_inception-2015-12-05-*.pth state dict; default: $XMC_FID_INCEPTION)')
+    parser.add_argument('--rprecision', action='store_true',
+                        help='score the sampled images: R-precision against their captions (RNN presets) -> manifest "r_precision"')
+    parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
+                        help="DAMSM image encoder weights for --rprecision (image_encoder100.pth; default: $XMC_DAMSM_IMAGE_ENCODER)")
+    parser.add_argument('--rp_k', type=int, default=100, metavar='K', help='--rprecision: candidates per image, the own caption included')
+    parser.add_argument('--rp_splits', type=int, default=10, metavar='S', help='--rprecision: parts the mean and its spread are taken over')
     # reranking
     parser.add_argument('--best_of', type=int, default=0, metavar='M',
                         help="draw M images per caption and keep the K the discriminator's conditional logit ranks highest (needs --netD)")
@@ -97,6 +104,13 @@ def _check_args(args):
             raise SystemExit(f'--fid_against: {args.fid_against} is neither an image directory nor an .npz statistics file')
         if not args.fid_inception or not os.path.isfile(args.fid_inception):
             raise SystemExit(f'--fid_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
+    if args.rprecision:
+        args.damsm_image_encoder = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
+        if not args.damsm_image_encoder or not os.path.isfile(args.damsm_image_encoder):
+            raise SystemExit(f'--rprecision needs the DAMSM image encoder weights: --damsm_image_encoder PATH or XMC_DAMSM_IMAGE_ENCODER '
+                             f'(got {args.damsm_image_encoder!r})')
+        if args.rp_k < 2 or args.rp_splits < 1:
+            raise SystemExit('--rp_k must be >= 2 and --rp_splits >= 1')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -104,6 +118,9 @@ def _check_args(args):
         cfg.TRAIN.BATCH_SIZE = args.bs
     if cfg.TRAIN.BATCH_SIZE < 1:
         raise SystemExit('--bs must be >= 1')
+    if args.rprecision and cfg.TEXT.ENCODER_NAME != 'RNN':
+        raise SystemExit(f"--rprecision pairs the DAMSM image encoder with the RNN caption encoder's sentence codes; TEXT.ENCODER_NAME is "
+                         f'{cfg.TEXT.ENCODER_NAME} (score the PNGs with xmc_gan/rprecision.py and a DAMSM text encoder instead)')
     if args.interp_sent and cfg.GEN.ENCODER_NAME != 'DF_GEN':
         raise SystemExit(f'--interp_sent moves the sentence embedding alone, which describes the caption only for a generator that ignores '
                          f'the word embeddings (DF_GEN); GEN.ENCODER_NAME is {cfg.GEN.ENCODER_NAME}')
@@ -225,6 +242,17 @@ def main(argv=None):
         from xmc_gan.utils.visual import fid_extractor
         from xmc_gan_amd.fid import FeatureStats, frechet_distance, stats_of
         fid_ex, fid_stats = fid_extractor(args.fid_inception, device), FeatureStats(device=device)
+    rp = rp_enc = None
+    if args.rprecision:
+        from xmc_gan_amd import rprecision as RP
+        try:
+            rp_enc = RP.load_image_encoder(args.damsm_image_encoder, None, device)
+        except (ImportError, ValueError) as e:
+            raise SystemExit(f'--damsm_image_encoder: {e}')
+        why = RP.usable_with(text_encoder, rp_enc)
+        if why:
+            raise SystemExit(f'--rprecision: {why}')
+        rp = RP.RPrecision(args.rp_k, args.rp_splits, args.seed)
     cap_step = max(1, bs // M)                                       # captions per batch: about `bs` forwards' worth of images
     try:
         for c0 in range(0, n, cap_step):
@@ -242,6 +270,8 @@ def main(argv=None):
                 kept[c0 * K:min(n_grid, c1 * K)] = x8[:n_grid - c0 * K]
             if fid_stats is not None:
                 fid_stats.update(fid_ex(u8))
+            if rp is not None:                                       # image r of the batch was made from caption r // K
+                rp.update(rp_enc.encode_u8(u8)[1], sents[c0:c1], torch.arange(nc).repeat_interleave(K))
             host = u8.cpu().numpy()                                  # one copy per batch: 3 bytes per pixel
             for r in range(nc * K):
                 c, k = c0 + r // K, r % K
@@ -281,10 +311,19 @@ def main(argv=None):
             raise SystemExit('--fid_against: a covariance needs at least two sampled images')
         fid = frechet_distance(*stats_of(args.fid_against, fid_ex, bs), *fid_stats.finalize())
         print(f'FID: {fid}')
+    r_precision = None
+    if rp is not None:
+        try:
+            r_precision = rp.finalize()
+        except ValueError as e:
+            raise SystemExit(f'--rprecision: {e}')
+        print(f'R-precision: {r_precision["r_precision"]} +- {r_precision["std"]} (k={r_precision["k"]}, n={r_precision["n"]})')
     manifest = dict(checkpoint=os.path.abspath(args.checkpoint), netD=os.path.abspath(args.netD) if args.netD else None,
                     cfg=os.path.abspath(args.cfg), config_name=cfg.CONFIG_NAME, generator=cfg.GEN.ENCODER_NAME, img_size=S,
                     seed=args.seed, precision=ops.precision(), truncation=args.truncation, n_per_caption=K, best_of=args.best_of or None,
                     captions=n, fid=fid, grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
+    if rp is not None:                                               # (only with --rprecision: the manifest of every other run is unchanged)
+        manifest['r_precision'] = r_precision
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

@@ -81,6 +81,9 @@ def parse_args(argv=None):
     parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
                         help="FID Inception weights (the pt_inception-2015-12-05-*.pth state dict of pytorch_fid): eval() scores on this "
                              "project's kernels (default: $XMC_FID_INCEPTION; without either, pytorch_fid if it is installed)")
+    parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
+                        help="DAMSM image encoder weights (image_encoder100.pth of AttnGAN's DAMSM archive): eval() also reports R-precision "
+                             "(RNN presets; default: $XMC_DAMSM_IMAGE_ENCODER; without either, no R-precision)")
     parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
                         help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (config.json, weights, tokenizer '
                              'files; default: $XMC_SBERT_DIR).  Without it the SBERT presets run with --synthetic only')
@@ -651,6 +654,20 @@ def _detached(last):
 _FID_INCEPTION = ['']        # --fid_inception (main()); eval() falls back to $XMC_FID_INCEPTION
 
 
+_DAMSM_IMAGE_ENCODER = ['']  # --damsm_image_encoder (main()); eval() falls back to $XMC_DAMSM_IMAGE_ENCODER
+_damsm_cache = {}
+
+
+def _damsm_encoder(path, device):
+    """the DAMSM image encoder of a weights file, loaded once per (file, device)"""
+    key = (os.path.abspath(path), os.stat(path).st_mtime_ns if os.path.isfile(path) else None, str(device))
+    if key not in _damsm_cache:
+        from xmc_gan_amd.rprecision import load_image_encoder
+        _damsm_cache.clear()
+        _damsm_cache[key] = load_image_encoder(path, None, device)
+    return _damsm_cache[key]
+
+
 def _fid_u8(images_nchw, device):
     """[B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] on the device: trunc((x + 1) * 127.5), the bytes eval() writes into the PNGs"""
     from xmc_gan_amd.fid import nchw_to_u8
@@ -669,13 +686,18 @@ def _real_stats(loader, extractor, device, limit):
 
 
 @torch.no_grad()
-def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None):
+def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
+         damsm_image_encoder=None, metrics=None):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to
     ``save_dir/<key>.png`` and, unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``,
     as 8-bit PNGs of (x + 1) * 127.5.  FID (logged and written to the scalar log as 'FID'):
     with ``fid_inception`` (default: --fid_inception, then $XMC_FID_INCEPTION) on this project's kernels -- the generated images go to the
     extractor from the device as the bytes the PNGs hold, the real images' statistics are computed once and cached beside ``org_dir`` as
     ``org_stats.npz`` (reused while its sample count matches); otherwise between the two directories when ``pytorch_fid`` is importable.
+    R-precision (logged, written as 'R_precision', and put into ``metrics`` when a dict is passed): with ``damsm_image_encoder`` (default:
+    --damsm_image_encoder, then $XMC_DAMSM_IMAGE_ENCODER), the DAMSM image encoder's weights -- the same bytes go through
+    ``CNN_ENCODER.encode_u8`` and are paired with the loop's ``sent_embs`` (k = 100 candidates, 10 splits; xmc_gan_amd/rprecision.py).  Only
+    with an ``RNN_ENCODER`` of the image encoder's width; otherwise one line says why it was not computed.
     Returns (uint8 tensor of the generated images, FID or None)."""
     from PIL import Image
     netG.eval()
@@ -697,6 +719,14 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
             cached = load_stats(cache, with_count=True)
         if cached is None:
             real_stats = FeatureStats(device=device)
+    damsm = damsm_image_encoder or _DAMSM_IMAGE_ENCODER[0] or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
+    image_encoder = rprec = rprec_why = None
+    if damsm:
+        from xmc_gan_amd import rprecision as RP
+        image_encoder = _damsm_encoder(damsm, device)
+        rprec_why = RP.usable_with(text_encoder, image_encoder)
+        if rprec_why is None:
+            rprec = RP.RPrecision()
     cnt, outs = 0, []
     for imgs, texts_lst, keys in loader:
         caps, cap_lens = texts_lst[0]
@@ -704,8 +734,11 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
+        fake_u8 = _fid_u8(fake, device) if (extractor is not None or rprec is not None) else None
+        if rprec is not None:
+            rprec.update(image_encoder.encode_u8(fake_u8)[1], sent_embs)
         if extractor is not None:
-            gen_stats.update(extractor(_fid_u8(fake, device)))
+            gen_stats.update(extractor(fake_u8))
             if real_stats is not None:
                 real_stats.update(extractor(_fid_u8(imgs, device)))
         for j in range(fake.size(0)):
@@ -736,6 +769,19 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         logger.info(f' epoch {state_epoch}, FID : {fid}')
         if writer is not None:
             writer.add_scalar('FID', fid, state_epoch)
+    if rprec is not None:
+        try:
+            r = rprec.finalize()
+        except ValueError as e:
+            r, rprec_why = None, str(e)
+        if r is not None:
+            logger.info(f' epoch {state_epoch}, R-precision : {r["r_precision"]} +- {r["std"]} (k={r["k"]}, n={r["n"]})')
+            if writer is not None:
+                writer.add_scalar('R_precision', r['r_precision'], state_epoch)
+            if metrics is not None:
+                metrics.update(r)
+    if rprec_why is not None:
+        logger.info(f' epoch {state_epoch}, R-precision not computed: {rprec_why}')
     return (torch.cat(outs) if outs else None), fid
 
 
@@ -772,6 +818,9 @@ def main(argv=None):
     _FID_INCEPTION[0] = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
     if _FID_INCEPTION[0] and not os.path.isfile(_FID_INCEPTION[0]):
         raise SystemExit(f'--fid_inception: {_FID_INCEPTION[0]} is not a file')
+    _DAMSM_IMAGE_ENCODER[0] = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
+    if _DAMSM_IMAGE_ENCODER[0] and not os.path.isfile(_DAMSM_IMAGE_ENCODER[0]):
+        raise SystemExit(f'--damsm_image_encoder: {_DAMSM_IMAGE_ENCODER[0]} is not a file')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', str(args.gpu_id)))
