@@ -50,7 +50,8 @@ extern "C" {
  *     xmc_image_to_u8 / xmc_image_minmax / xmc_image_grid_u8 (csrc/image.hip);
  *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip);
  *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip);
- *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip). */
+ *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip);
+ *     xmc_crop_flip_normalize (csrc/datafeed.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -739,6 +740,18 @@ int xmc_fid_moments(const float* x, double* sum, double* outer, int B, int D, vo
  * XMC_EINVAL: img / txt / cand / rank NULL or N, M, K < 1; XMC_ESHAPE: D % 4 != 0, D < 4 or D > 1024; XMC_EALIGN: img / txt not 16-byte
  * aligned.  All refused before any launch. */
 int xmc_rprecision(const float* img, const float* txt, const int32_t* cand, int32_t* rank, float* score, int N, int M, int K, int D, void* stream);
+
+/* ---- training batches out of a device-resident uint8 image pool (csrc/datafeed.hip; xmc_gan_amd/imagecache.py) ---------------------------
+ * pool: `pool_bytes` bytes of RGB HWC images back to back, image i at byte offsets[i] (int64 [N]) with hw[i] = (height, width) (int32 [N,2]).
+ * params int32 [B,4] = (image index, top, left, flip); table f32 [256] = the host's normalisation of the bytes 0..255.
+ *   out f32 [B,3,S,S] (NCHW):  out[b][c][y][x] = table[pool[offsets[i] + ((top + y) * w + left + (flip ? S-1-x : x)) * 3 + c]]
+ * A look-up, no arithmetic on the value: bit-equal to Image.crop + FLIP_LEFT_RIGHT + to_normalized_tensor of xmc_gan/dataset.py.
+ * The CALLER checks params (0 <= i < N, 0 <= top <= h - S, 0 <= left <= w - S); whatever it is handed, the kernel reads offsets / hw at an
+ * index clamped to [0, N) and the pool in whole 16-byte units clamped to [0, pool_bytes / 16), and writes exactly B*3*S*S floats.
+ * XMC_EINVAL: a NULL pointer, N < 1, pool_bytes < 16 or not a multiple of 16.  XMC_ESHAPE: B < 1, S < 8, S % 8 != 0, S > 1024.
+ * XMC_EALIGN: pool or out not 16-byte aligned, offsets not 8-byte aligned.  All refused before any launch.  No atomics. */
+int xmc_crop_flip_normalize(const uint8_t* pool, int64_t pool_bytes, const int64_t* offsets, const int32_t* hw, int N, const int32_t* params,
+                            const float* table, float* out, int B, int S, void* stream);
 
 #ifdef __cplusplus
 }

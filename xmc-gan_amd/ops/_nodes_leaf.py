@@ -1,5 +1,6 @@
 """xmc_gan_amd.ops, layer 3: the leaf nodes.  Pointwise, pooling and layout Functions whose backward is written with Functions of
 this same module, and from which the later node modules build theirs.  Imports `_config` and `_engine`."""
+import numpy as np
 import torch
 from .. import lib as L
 from ._config import _code, _need_cuda, _p, _st, act_dtype, fused_blocks
@@ -337,6 +338,94 @@ def image_grid_u8(x8, nrow=8, padding=2, out=None):
     parts = torch.empty((N, L.DIFFAUG_PARTS, 2), dtype=torch.float32, device=x8.device)
     L.call("xmc_image_minmax", _p(x8), _p(parts), N, H, W, _code(x8.dtype), _st())
     L.call("xmc_image_grid_u8", _p(x8), _p(parts), _p(out), N, H, W, nrow, padding, _code(x8.dtype), _st())
+    return out
+
+
+# ------------------------------------------------------------------------------------------ training batches from a uint8 image pool (csrc/datafeed.hip)
+class HostMirror:
+    """A small integer array that lives twice: ``host`` (numpy, drawn or loaded there) and ``dev`` (its device copy, what a kernel reads).
+    `crop_flip_normalize` checks the host copy before it launches on the device copy, without a read-back."""
+
+    def __init__(self, host, device=None, dev=None):
+        """``device``: upload ``host`` there; or ``dev``: the device copy that already exists (a slice of a larger upload)"""
+        self.host = np.ascontiguousarray(host)
+        self.dev = torch.from_numpy(self.host).to(device) if dev is None else dev
+
+
+def validate_crop_params(params, hw, size):
+    """The bounds `crop_flip_normalize` needs, checked on host arrays: params int32 [B,4] = (image index, top, left, flip) against
+    hw int32 [N,2] = (height, width): 0 <= index < N, 0 <= top <= h - size, 0 <= left <= w - size, flip in {0, 1}.  ValueError names the
+    first offending row."""
+    params, hw = np.asarray(params), np.asarray(hw)
+    if params.ndim != 2 or params.shape[1] != 4 or params.shape[0] < 1 or params.dtype != np.int32:
+        raise ValueError(f"crop params: int32 [B,4] with B >= 1 expected, got {params.dtype} {params.shape}")
+    if hw.ndim != 2 or hw.shape[1] != 2 or hw.shape[0] < 1 or hw.dtype != np.int32:
+        raise ValueError(f"crop params: hw int32 [N,2] with N >= 1 expected, got {hw.dtype} {hw.shape}")
+    p = params.astype(np.int64)
+    idx, top, left, flip = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+    bad = (idx < 0) | (idx >= hw.shape[0])
+    h, w = hw[np.where(bad, 0, idx)].astype(np.int64).T
+    bad |= (top < 0) | (top > h - size) | (left < 0) | (left > w - size) | (flip < 0) | (flip > 1)
+    if bad.any():
+        b = int(np.argmax(bad))
+        dims = "no such image" if not 0 <= idx[b] < hw.shape[0] else f"image {h[b]} x {w[b]}"
+        raise ValueError(f"crop params: row {b} = (index {idx[b]}, top {top[b]}, left {left[b]}, flip {flip[b]}) is out of range for a "
+                         f"{size} x {size} crop ({dims}, {hw.shape[0]} images)")
+
+
+_norm_tables = {}
+
+
+def normalize_table(device=None):
+    """f32 [256]: `xmc_gan.dataset.to_normalized_tensor` of the bytes 0..255, computed by that function on the host (once) and, with a
+    ``device``, uploaded (once per device): what `crop_flip_normalize` looks pixels up in"""
+    if "host" not in _norm_tables:
+        from xmc_gan.dataset import to_normalized_tensor
+        _norm_tables["host"] = to_normalized_tensor(np.arange(256, dtype=np.uint8).reshape(16, 16)).reshape(256).contiguous()
+    if device is None:
+        return _norm_tables["host"]
+    key = str(torch.device(device))
+    if key not in _norm_tables:
+        _norm_tables[key] = _norm_tables["host"].to(device)
+    return _norm_tables[key]
+
+
+def crop_flip_normalize(pool, offsets, hw, params, size, out=None, table=None):
+    """B crops out of a device-resident pool of uint8 RGB HWC images -> f32 NCHW [B,3,size,size], the `imgs` of a training step:
+    out[b,c,y,x] = table[pool[offsets[i] + ((top + y) * w + left + (flip ? size-1-x : x)) * 3 + c]] with (i, top, left, flip) = params[b].
+
+    ``pool`` uint8 [bytes] (16-byte aligned, a multiple of 16 bytes), ``offsets`` int64 [N], both on the device; ``hw`` a `HostMirror` of
+    int32 [N,2] (height, width); ``params`` a `HostMirror` of int32 [B,4], or the host array (uploaded here).  ``table``: f32 [256] on the
+    device (default: `normalize_table`).  The host copies are checked (`validate_crop_params`) BEFORE anything is launched; a violation
+    is a ValueError.  One launch on the current stream into a new tensor or the caller's ``out``.  size % 8 == 0."""
+    if not isinstance(hw, HostMirror):
+        raise TypeError("crop_flip_normalize: hw must be an ops.HostMirror (the bounds are checked on its host copy)")
+    _need_cuda(pool, offsets, hw.dev)
+    if not isinstance(params, HostMirror):
+        if torch.is_tensor(params) and params.is_cuda:
+            raise TypeError("crop_flip_normalize: params must come with their host copy (an ops.HostMirror or a host array)")
+        host = params.numpy() if torch.is_tensor(params) else np.asarray(params)
+        validate_crop_params(host, hw.host, int(size))
+        params = HostMirror(host, pool.device)
+    else:
+        validate_crop_params(params.host, hw.host, int(size))
+    size, N, B = int(size), hw.host.shape[0], params.host.shape[0]
+    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise ValueError(f"crop_flip_normalize: pool must be a contiguous uint8 vector, got {pool.dtype} {tuple(pool.shape)}")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (N,) or not offsets.is_contiguous():
+        raise ValueError(f"crop_flip_normalize: offsets int64 [{N}] expected, got {offsets.dtype} {tuple(offsets.shape)}")
+    if hw.dev.dtype != torch.int32 or params.dev.dtype != torch.int32 or tuple(params.dev.shape) != (B, 4) or tuple(hw.dev.shape) != (N, 2):
+        raise ValueError("crop_flip_normalize: the device copies of hw / params do not match their host copies")
+    table = normalize_table(pool.device) if table is None else table
+    _need_cuda(table, params.dev)
+    if table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous():
+        raise ValueError("crop_flip_normalize: table must be a contiguous f32 [256]")
+    shape = (B, 3, size, size)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=pool.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != pool.device:
+        raise ValueError(f"crop_flip_normalize: out must be a contiguous f32 {shape} tensor on {pool.device}")
+    L.call("xmc_crop_flip_normalize", _p(pool), pool.numel(), _p(offsets), _p(hw.dev), N, _p(params.dev), _p(table), _p(out), B, size, _st())
     return out
 
 

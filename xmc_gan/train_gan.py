@@ -90,6 +90,9 @@ def parse_args(argv=None):
     parser.add_argument('--diffaug', type=str, default='',
                         help="differentiable augmentation of every image the discriminator sees: comma list out of color, translation, "
                              "cutout (typical: all three).  '' (default): off")
+    parser.add_argument('--image_cache', type=str, default='', metavar='DIR',
+                        help='train and evaluate from the uint8 image cache in DIR (built by xmc_gan/image_cache.py): the resized images '
+                             'stay in device memory and a batch is one crop + flip + normalise launch instead of the PIL DataLoader')
     return parser.parse_args(argv)
 
 
@@ -806,6 +809,8 @@ def main(argv=None):
         aug_policy = parse_policy(args.diffaug)
     except ValueError as e:
         raise SystemExit(f'--diffaug: {e}')
+    if args.image_cache and args.synthetic > 0:
+        raise SystemExit('--image_cache and --synthetic exclude each other')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -857,6 +862,21 @@ def main(argv=None):
     if args.synthetic > 0:
         train_loader = SyntheticCOCO(args.synthetic, cfg.TRAIN.BATCH_SIZE, cfg.IMG.SIZE, cfg.TEXT.MAX_LENGTH, seed,
                                      cfg.TEXT.VOCA_SIZE)
+    elif args.image_cache:      # the same items out of a device-resident uint8 cache (xmc_gan_amd/imagecache.py): no image is opened here
+        from xmc_gan_amd.imagecache import DeviceImageLoader, ImageCache
+        data_dir = args.data_dir or f'{PROJ_DIR}/data/{cfg.DATASET_NAME}'
+        data_arch = _TEXT_DATASET[cfg.TEXT.TYPE]
+        loaders = {}
+        for mode in ('train', 'test'):
+            text_set = data_arch(data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
+            try:
+                cache = ImageCache.load(args.image_cache, mode, cfg.IMG.SIZE, text_set.filenames, data_dir=data_dir)
+            except ValueError as e:
+                raise SystemExit(f'--image_cache: {e}')       # (the message ends with the command that builds this split's cache)
+            loaders[mode] = DeviceImageLoader(cache, text_set, cfg.TRAIN.BATCH_SIZE, device, train=mode == 'train', seed=args.seed,
+                                              rank=rank, world=world, start_epoch=args.resume_epoch)
+            logger.info(f'image cache {cache.u8_path}: {len(cache)} images, {cache.nbytes} bytes on the device')
+        train_loader, test_loader = loaders['train'], loaders['test']
     else:       # the reference's loaders (train_gan.py:440-457); each rank draws its own shuffled batches
         data_dir = args.data_dir or f'{PROJ_DIR}/data/{cfg.DATASET_NAME}'
         data_arch = _TEXT_DATASET[cfg.TEXT.TYPE]
