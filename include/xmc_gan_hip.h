@@ -51,7 +51,8 @@ extern "C" {
  *     xmc_roberta_embed_ln / xmc_add_layernorm / xmc_attention_short / xmc_bias_gelu / xmc_sbert_pool (csrc/transformer.hip);
  *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip);
  *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip);
- *     xmc_crop_flip_normalize (csrc/datafeed.hip). */
+ *     xmc_crop_flip_normalize (csrc/datafeed.hip);
+ *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -274,6 +275,17 @@ int xmc_conv_ptile_bits(const XmcConvDesc* d, void* stream);
  * (16 extra MFMAs per wave) instead of read from d->res (must be NULL).  1 = not this kernel's shape. */
 int xmc_conv_ptile_scimg(const XmcConvDesc* d, void* stream);
 int xmc_conv_wgrad_bits(const XmcConvDesc* d, float* dwp, void* stream);
+/* The backward of the generator's tail, LeakyReLU -> conv_out (32 -> <= 4 channels, 3x3, pad 1) -> tanh (df_gan.py:84-88), in ONE pass
+ * over conv_out's input y.  `d` is the descriptor of conv_out's data gradient as xmc_conv_igemm takes it (mask = y, optional dst_pool),
+ * except that d->src is dy, the gradient of the tanh IMAGE, and `img` that image (both [N,H,W,8], the 16-bit format): the kernel forms
+ * dpre = dy * (1 - img^2), rounded as xmc_tanh_bwd rounds it, where it stages the operand.  d->dst / d->dst_pool receive what
+ * xmc_tanh_bwd + xmc_conv_igemm write today, bit for bit.  dwp != NULL: also conv_out's weight gradient, accumulated into
+ * dwp f32 [9][dw_rows][32] (the packed layout of xmc_conv_wgrad, rows 0..3 of each tap; zeroed by the caller), and with dbias != NULL
+ * its bias gradient into f32 [XMC_BIAS_REPLICAS][8] (as xmc_conv_wgrad_bias).  grid_cap > 0 limits the persistent grid
+ * (tests: several tiles per workgroup on small maps).  Returns 1 and launches nothing for what the kernel does not take (f32, y channels != 32, H % 8 != 0, odd W, a
+ * descriptor with bias / act / res / ...; XMC_DEBUG_DISPATCH=no_gtail_fused): the caller then runs xmc_tanh_bwd, xmc_conv_wgrad_bias
+ * and xmc_conv_igemm. */
+int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, float* dbias, int dw_rows, int grid_cap, void* stream);
 int xmc_tanh_bwd(const void* dy, const void* y, void* dx, int64_t n, int dtype, void* stream);
 /* y = a + (*alpha_dev) * b                  (shortcut + gamma*residual, df_gan.py:200,284) */
 int xmc_axpby(const void* a, const void* b, const float* alpha_dev, void* y, int64_t n, int dtype, void* stream);

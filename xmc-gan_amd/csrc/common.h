@@ -70,6 +70,14 @@ __device__ __forceinline__ bf16x4 xmc_ds_read_tr16(const void* p) {
     return __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xmc_s16x4*)(p)));
 }
 
+// `v` as an f32 value in a register of its own.  A product that is converted to IEEE half right away may be selected as ONE instruction
+// (v_fma_mixlo_f16: rounds the exact product once) or as multiply + convert (rounds twice); which one is the compiler's choice per
+// call site -- thin_in_kernel<32>'s masked epilogue had it on one of a lane's eight channels.  Kernels that promise each other's bits
+// (gtail_bwd_kernel and the launches it replaces, conv_thin.hip / xmc_tanh_bwd) pin the product first: always f32, then one conversion.
+__device__ __forceinline__ float xmc_pin_f32(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
 __device__ __forceinline__ float lrelu_f(float v) { return v > 0.f ? v : XMC_LRELU * v; }
 // tanh for results that are stored as bf16: 1 - 2 / (exp(2x) + 1) on the hardware exp2 / rcp (absolute error ~1e-7, far below
 // half a bf16 ulp of the result; libm's tanhf costs ~0.7 ms on the generator's 256x256 output layer).  The f32 parity mode
@@ -79,6 +87,9 @@ __device__ __forceinline__ float tanh_fast(float v) {
     return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 __device__ __forceinline__ float lrelu_slope(float ref) { return ref > 0.f ? 1.f : XMC_LRELU; }
+// dx = dy * tanh'(x) from y = tanh(x): ONE spelling for xmc_tanh_bwd and for the kernel that applies it while it stages dy
+// (conv_thin.hip, gtail_bwd_kernel), pinned (xmc_pin_f32) so that both round the same f32 value to 16 bits
+__device__ __forceinline__ float tanh_bwd_f(float dy, float y) { return xmc_pin_f32(dy * (1.f - y * y)); }
 // one 16-byte unit (8 channels) x LeakyReLU' from its sign byte (bit k set: channel k positive), rounded back to the 16-bit format:
 // what xmc_signmask_apply stores, computed where the unit is staged (XmcConvDesc.mask_bits)
 __device__ __forceinline__ u32x4 xmc_apply_sign_bits(u32x4 v, unsigned b) {

@@ -143,8 +143,8 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const XmcConvDesc d, const
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const float x0 = acc[2 * u][q] + bias8[u][q], x1 = acc[2 * u + 1][q] + bias8[u][4 + q];
-                            o[q] = (xmc_h16)(fmaxf(x0, x0 * slope) * lrelu_slope((float)mk[q]));
-                            o[4 + q] = (xmc_h16)(fmaxf(x1, x1 * slope) * lrelu_slope((float)mk[4 + q]));
+                            o[q] = (xmc_h16)xmc_pin_f32(fmaxf(x0, x0 * slope) * lrelu_slope((float)mk[q]));          // pinned: gtail_bwd_kernel
+                            o[4 + q] = (xmc_h16)xmc_pin_f32(fmaxf(x1, x1 * slope) * lrelu_slope((float)mk[4 + q]));  // promises these bits
                         }
                     }
                     dst8[dbase + eoff[i] + u] = o;
@@ -168,6 +168,223 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const XmcConvDesc d, const
                     if ((fr & 1) == 0) pool8[((img * (d.DH >> 1) + prow) * (d.DW >> 1) + pcol) * cd8 + fc * UPL + u] = o;
                 }
             }
+        }
+    }
+}
+
+// ---- The backward of the generator's tail (LeakyReLU -> conv_out 32 -> 3 -> tanh, df_gan.py:84-88) as ONE pass over its 32-channel
+// activation y (ops.GBlockEndFn.backward).  thin_in_kernel<32> as conv_out's data gradient already holds, per tile, both
+// operands of conv_out's WEIGHT gradient: the (8+2)x(32+2) patch of its source dpre = dy * tanh'(img) in LDS and, for the mask of
+// its epilogue, y at exactly the tile's pixels.  Written over the positions q of y,
+//     dW[tap][co][ci] = sum_q y[q][ci] * dpre[q + (dh, dw)(tap)][co]          ((dh, dw)(tap): the data gradient's own tap shift)
+// needs no halo of y, and the patch's zero padding supplies the border terms.  So this kernel
+//   * stages dpre itself from dy and img (xmc_tanh_bwd's arithmetic and rounding, applied to the 16-byte unit on its way into LDS:
+//     dpre is never written), then runs thin_in_kernel<32>'s MFMAs, mask, stores and 2x2 sum pool unchanged: dz and dsc come out
+//     bit-identical;
+//   * WG: each wave passes the y units of its 2 x 16 pixels per half-tile through 3 KB of LDS of its own and reads them back pixel-
+//     major (ds_read_b64_tr_b16, as conv_wgrad.hip) as the B operand of a [12 tap slots x 4 channels] x [32 ci] x [32 pixels] product,
+//     whose A operand is the same transposing read on the patch at the tap-shifted pixel (the first 8 bytes of a pixel: conv_out has
+//     <= 4 output channels); 24 accumulator registers per lane live across the persistent tile loop, the four waves meet in LDS
+//     at the end and the workgroup issues 1152 f32 atomics into the packed buffer of the weight-gradient kernels.  The bias
+//     gradient is the sum of the centre tap's A fragments;
+//   * takes a partial last tile in x (any even W), which the unfused kernel declines.
+constexpr int GT_YSTR = 96;          // bytes per pixel of the y image: 64 + 32, the transposing reads of a 32-lane half then cover all banks once
+// Registers: WG needs 138 (no scratch) -> 3 workgroups per CU.  Bound to 4 per CU it spills one register and, at grids equal to what is
+// resident (1024 / 768 workgroups), runs no faster (0.593 / 0.598 ms at 256 x 256x256); a grid beyond the resident set costs 20 %.
+template <bool WG>
+__global__ __launch_bounds__(256, WG ? 3 : 4) void gtail_bwd_kernel(const XmcConvDesc d, const u32x4* __restrict__ img16, float* __restrict__ dwp,
+                                                        float* __restrict__ dbias, int dw_rows, int tiles_y, int tiles_x, int ntiles) {
+    constexpr int TH = 8, TW = 32, PW = TW + 2, PH = TH + 2, KS = 3, TN = 2, NRED = 9 * 4 * 32;
+    __shared__ __attribute__((aligned(16))) unsigned char patch[PH * PW * 16];
+    __shared__ __attribute__((aligned(16))) unsigned char ylds[WG ? 4 * 32 * GT_YSTR : 16];
+    static_assert(!WG || 4 * 32 * GT_YSTR >= NRED * 4, "the cross-wave reduction reuses the y image");
+    const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
+    const int fr = lane & 15, fc = lane >> 4;
+    const u32x4* __restrict__ dy16 = reinterpret_cast<const u32x4*>(d.src);
+    const u32x4* __restrict__ w16 = reinterpret_cast<const u32x4*>(d.wpk);
+
+    // data-gradient weights -> registers, exactly as thin_in_kernel<32> (K-step ks, lane group fc <-> tap 4*ks + fc)
+    u32x4 wf[KS][TN];
+    int toff[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int tap = ks * 4 + fc;
+        const bool live = tap < 9;
+        const int tt = live ? tap : 0;
+        toff[ks] = ((d.dh[0][tt] + 1) * PW + (d.dw[0][tt] + 1)) * 16;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int lrow = (fr >> 2) * 8 + j * 4 + (fr & 3);
+            wf[ks][j] = live ? w16[(size_t)d.wi[0][tt] * d.CDw + lrow] : u32x4{0, 0, 0, 0};
+        }
+    }
+    // patch staging: thread -> up to 2 patch pixels
+    int ppix[2], ppy[2], ppx[2];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int pp = tid + it * 256;
+        ppy[it] = pp / PW; ppx[it] = pp - ppy[it] * PW;
+        ppix[it] = pp < PH * PW ? pp : -1;
+    }
+    int pbase[4], eoff[4];
+    const int cd8 = 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = wm * 2 + (i >> 1), c = (i & 1) * 16 + fr;
+        pbase[i] = (r * PW + c) * 16;
+        eoff[i] = (r * d.DW + c) * cd8 + fc;
+    }
+    // weight gradient: lane 4q + pp of a 16-lane group addresses K row (pixel) 4*fc + q [+16], 4 elements of column block pp
+    const int tq = fr >> 2, tp = fr & 3;
+    int aoff[3];                                  // A: tap slot tp of row block j <-> tap 4j + tp (slots of taps >= 9: any valid address, rows dropped)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int tap = 4 * j + tp < 9 ? 4 * j + tp : 0;
+        aoff[j] = ((wm * 2 + d.dh[0][tap] + 1) * PW + (4 * fc + tq + d.dw[0][tap] + 1)) * 16;
+    }
+    unsigned char* const ywave = ylds + (WG ? wm * 32 * GT_YSTR : 0);
+    const int ywr = fr * GT_YSTR + fc * 16;                     // + h * 16 rows: this lane's unit of pixel (row h, column fr) of the half-tile
+    const int yrd = (4 * fc + tq) * GT_YSTR + tp * 8;           // + 32 bytes per 16-channel block, + 16 rows for the second half of the K step
+    f32x4 accw[3][2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) accw[j][0] = accw[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+
+    const int tpi = tiles_y * tiles_x;
+    bf16x8* __restrict__ dst8 = reinterpret_cast<bf16x8*>(d.dst);
+    const bf16x8* __restrict__ mask8 = reinterpret_cast<const bf16x8*>(d.mask);
+    const float pscale = d.pool_scale == 0.f ? 0.25f : d.pool_scale;
+
+    u32x4 pvd[2], pvi[2];
+    auto issue = [&](int tile) {
+        const int img = tile / tpi, trem = tile - img * tpi;
+        const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int gy = ty * TH - 1 + ppy[it], gx = tx * TW - 1 + ppx[it];
+            const bool ok = ppix[it] >= 0 && (unsigned)gy < (unsigned)d.SH && (unsigned)gx < (unsigned)d.SW;
+            const unsigned idx = ok ? (unsigned)((img * d.SH + gy) * d.SW + gx) : 0u;
+            const u32x4 z = {0, 0, 0, 0};
+            pvd[it] = ok ? dy16[idx] : z;
+            pvi[it] = ok ? img16[idx] : z;
+        }
+    };
+    const XcdWalk xw = xmc_xcd_walk(ntiles);
+    int tile = xw.first;
+    if (tile < xw.end) issue(tile);
+    for (; tile < xw.end; tile += xw.step) {
+        const int img = tile / tpi, trem = tile - img * tpi;
+        const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+        __syncthreads();                          // previous tile's reads are done
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const bf16x8 a = __builtin_bit_cast(bf16x8, pvd[it]), b = __builtin_bit_cast(bf16x8, pvi[it]);
+            bf16x8 v;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = (xmc_h16)tanh_bwd_f((float)a[k], (float)b[k]);      // (0, 0) outside the image -> 0
+            if (ppix[it] >= 0) *reinterpret_cast<bf16x8*>(patch + ppix[it] * 16) = v;
+        }
+        __syncthreads();
+        if (tile + xw.step < xw.end) issue(tile + xw.step);
+        const int dbase = ((img * d.DH + ty * TH) * d.DW + tx * TW) * cd8;
+#pragma unroll
+        for (int ip = 0; ip < 2; ++ip) {
+            const bool colok = tx * TW + ip * 16 + fr < d.DW;        // partial last tile in x
+            bf16x8 mk[2], fin[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int i = ip + 2 * h;
+                f32x4 acc[TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const u32x4 pf = *reinterpret_cast<const u32x4*>(patch + pbase[i] + toff[ks]);
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[j] = XMC_MFMA_16x16x32(__builtin_bit_cast(bf16x8, wf[ks][j]), __builtin_bit_cast(bf16x8, pf), acc[j], 0, 0, 0);
+                }
+                const bf16x8 zero8 = __builtin_bit_cast(bf16x8, u32x4{0, 0, 0, 0});
+                mk[h] = colok ? mask8[dbase + eoff[i]] : zero8;
+                bf16x8 o;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {       // thin_in_kernel's epilogue with no bias and no activation (acc + 0: -0 -> +0 as there)
+                    const float x0 = acc[0][q] + 0.f, x1 = acc[1][q] + 0.f;
+                    o[q] = (xmc_h16)xmc_pin_f32(x0 * lrelu_slope((float)mk[h][q]));
+                    o[4 + q] = (xmc_h16)xmc_pin_f32(x1 * lrelu_slope((float)mk[h][4 + q]));
+                }
+                if (colok) dst8[dbase + eoff[i]] = o;
+                fin[h] = o;
+            }
+            if (d.dst_pool) {
+                bf16x8* __restrict__ pool8 = reinterpret_cast<bf16x8*>(d.dst_pool);
+                const int prow = ty * (TH / 2) + wm, pcol = tx * (TW / 2) + ((ip * 16 + fr) >> 1);
+                bf16x8 o;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    float sm = (float)fin[0][q] + (float)fin[1][q];
+                    sm += xmc_xor1(sm);
+                    o[q] = (xmc_h16)(pscale * sm);
+                }
+                if ((fr & 1) == 0 && colok) pool8[((img * (d.DH >> 1) + prow) * (d.DW >> 1) + pcol) * cd8 + fc] = o;
+            }
+            if constexpr (WG) {
+                // K step = the 32 pixels (rows 2*wm, 2*wm + 1) x (columns 16*ip .. +15) this wave just finished; all 64 lanes take part
+                // (the transposing reads need EXEC all ones); y of a column beyond the image is 0
+                *reinterpret_cast<bf16x8*>(ywave + ywr) = mk[0];
+                *reinterpret_cast<bf16x8*>(ywave + ywr + 16 * GT_YSTR) = mk[1];
+                __builtin_amdgcn_wave_barrier();
+                bf16x8 af[3], bq[2];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const unsigned char* base = patch + aoff[j] + ip * 16 * 16;
+                    const bf16x4 lo = xmc_ds_read_tr16(base), hi = xmc_ds_read_tr16(base + PW * 16);
+                    af[j] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const unsigned char* base = ywave + yrd + i * 32;
+                    const bf16x4 lo = xmc_ds_read_tr16(base), hi = xmc_ds_read_tr16(base + 16 * GT_YSTR);
+                    bq[i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                }
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) accw[j][i] = XMC_MFMA_16x16x32(af[j], bq[i], accw[j][i], 0, 0, 0);
+                // bias gradient: slot 0 of row block 1 is the centre tap (4), i.e. dpre at the 32 pixels themselves
+#pragma unroll
+                for (int k = 0; k < 8; ++k) bsum += (float)af[1][k];
+                __builtin_amdgcn_wave_barrier();          // the next half-tile's y units are written after these reads
+            }
+        }
+    }
+    if constexpr (WG) {
+        // D[row = 4 * slot + co][col = ci]: lane (fr, fc) holds slot fc (tap 4j + fc), co = r, ci = 16 i + fr.  Four waves -> one sum in LDS,
+        // then 128-byte rows of atomics into dwp[tap][co][ci] (the layout xmc_unpack_wgrad* reads)
+        float* const red = reinterpret_cast<float*>(ylds);
+        __syncthreads();
+        for (int id = tid; id < NRED; id += 256) red[id] = 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int tap = 4 * j + fc;
+            if (tap < 9) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) atomicAdd(&red[(tap * 4 + r) * 32 + i * 16 + fr], accw[j][i][r]);
+            }
+        }
+        __syncthreads();
+        for (int id = tid; id < NRED; id += 256) {
+            const int tap = id >> 7, co = (id >> 5) & 3, ci = id & 31;
+            atomicAdd(&dwp[((size_t)d.wi[0][tap] * dw_rows + co) * 32 + ci], red[id]);
+        }
+        if (dbias) {
+            float v = tp == fr ? bsum : 0.f;           // lanes fr < 4 of each group: slot 0, channel fr
+            v += __shfl_xor(v, 16, 64);
+            v += __shfl_xor(v, 32, 64);
+            if (lane < 4) atomicAdd(&dbias[(blockIdx.x & (XMC_BIAS_REPLICAS - 1)) * d.CS + lane], v);
         }
     }
 }
@@ -561,6 +778,36 @@ int xmc_conv_thin_try(const XmcConvDesc* d, void* stream) {
         hipLaunchKernelGGL((thin_in_kernel<64>), dim3(xmc_ab_grid(gx)), dim3(256), 0, st, *d, t, ntiles);
     }
     xmc_note_kernel("thin_in_kernel<%d>", d->CDw);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
+// The generator tail's backward in one pass (gtail_bwd_kernel; include/xmc_gan_hip.h).  0 = launched, 1 = not this kernel's case, < 0 = error
+extern "C" int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, float* dbias, int dw_rows, int grid_cap, void* stream) {
+    if (!d || !d->src || !d->wpk || !d->dst || !d->mask || !img) return XMC_EINVAL;
+    if (d->N < 1 || d->MH < 1 || d->MW < 1 || d->ntaps < 1 || d->ntaps > XMC_MAX_TAPS) return XMC_ESHAPE;
+    if (dwp && (dw_rows < 4 || dw_rows % 4 != 0)) return XMC_ESHAPE;
+    if (d->mask_bits || d->sc_img || d->wpk_lo) return XMC_EINVAL;
+    static const bool off = xmc_debug_off("no_gtail_fused");
+    if (off) return 1;
+    if (d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16 || d->CS != 8 || d->CD != 32 || d->CDw != 32) return 1;
+    if (d->SA != 1 || d->DA != 1 || d->src_shift != 0 || d->nclass != 1 || d->ntaps != 9 || d->groups > 1) return 1;
+    if (d->bias || d->res || d->alpha_dev || d->dst2 || d->post_act || d->sign_bits || d->dot || d->act != XMC_ACT_NONE) return 1;
+    if (d->MH % 8 != 0 || d->MW % 2 != 0 || d->SH != d->MH || d->SW != d->MW || d->DH != d->MH || d->DW != d->MW) return 1;
+    if (d->dph[0] != 0 || d->dpw[0] != 0) return 1;
+    for (int t = 0; t < 9; ++t)         // the 3x3, pad-1 data gradient in its natural tap order: tap t reads dpre at (+1 - t / 3, +1 - t % 3)
+        if (d->dh[0][t] != 1 - t / 3 || d->dw[0][t] != 1 - t % 3 || d->wi[0][t] != t) return 1;
+    const int tiles_y = d->MH / 8, tiles_x = (d->MW + 31) / 32;
+    if ((int64_t)d->N * d->MH * d->MW * 4 >= (1ll << 31) || (int64_t)d->N * tiles_y * tiles_x >= (1ll << 30)) return 1;
+    const int ntiles = d->N * tiles_y * tiles_x;
+    int gx = 256 * (dwp ? 3 : 5);       // the resident set (see the kernel's register note); without the weight gradient as thin_in_kernel
+    if (grid_cap > 0 && gx > grid_cap) gx = grid_cap;
+    if (gx > ntiles) gx = ntiles;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const u32x4* img16 = reinterpret_cast<const u32x4*>(img);
+    if (dwp) hipLaunchKernelGGL((gtail_bwd_kernel<true>), dim3(xmc_ab_grid(gx)), dim3(256), 0, st, *d, img16, dwp, dbias, dw_rows, tiles_y, tiles_x, ntiles);
+    else hipLaunchKernelGGL((gtail_bwd_kernel<false>), dim3(xmc_ab_grid(gx)), dim3(256), 0, st, *d, img16, nullptr, nullptr, 0, tiles_y, tiles_x, ntiles);
+    xmc_note_kernel("gtail_bwd_kernel<%d>", dwp ? 1 : 0);
     XMC_LAUNCH_CHECK();
     return 0;
 }

@@ -68,7 +68,7 @@ __global__ void map2_kernel(const void* a, const void* b, void* y, int64_t n8, F
 struct FLrelu { float slope; __device__ float operator()(float v) const { return v > 0.f ? v : slope * v; } };
 struct FTanh { __device__ float operator()(float v) const { return tanhf(v); } };
 struct FLreluMask { float slope; __device__ float operator()(float dy, float ref) const { return ref > 0.f ? dy : slope * dy; } };
-struct FTanhBwd { __device__ float operator()(float dy, float y) const { return dy * (1.f - y * y); } };
+struct FTanhBwd { __device__ float operator()(float dy, float y) const { return tanh_bwd_f(dy, y); } };
 struct FAxpby { const float* alpha; __device__ float operator()(float a, float b) const { return a + (*alpha) * b; } };
 struct FScale { const float* alpha; __device__ float operator()(float v) const { return (*alpha) * v; } };
 

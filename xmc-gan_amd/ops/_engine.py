@@ -417,6 +417,41 @@ def _conv_dgrad_raw(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=
     staged = dy if isinstance(dy, _StagedMask) else None        # dy x LeakyReLU'(bits), masked where the kernel stages it
     if staged is not None:
         dy = staged.dy
+    d, dx, dxp, wpk = _dgrad_desc(dy, w, geom, in_hw, in_dtype, mask, res, res_rows, res_scale, alpha, want_sumpool, dot)
+    N, OH, OW, CDy = dy.shape
+    H, W = in_hw
+    if src_bits is not None:
+        # ``src_bits`` (sign bytes in dy's layout): also return dy x LeakyReLU'(bits).  The streaming 1x1 kernels write it while they
+        # read dy (xmc_conv_pw1x1_masked_src); any other shape runs the data gradient and the mask pass separately.
+        assert geom.k == 1 and geom.s == 1 and not want_sumpool and src_bits.dtype == torch.uint8 and src_bits.numel() * 8 == dy.numel()
+        dym = torch.empty_like(dy)
+        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin,
+                         f"dgrad+srcmask {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k1s1", _nbytes(dy, wpk, dx, dym)):
+            rc = L.load().xmc_conv_pw1x1_masked_src(C.byref(d), _p(src_bits), _p(dym), 0.2, _st())
+            if rc == 1:
+                _igemm(d, "xmc_conv_igemm(dgrad)")
+                L.call("xmc_signmask_apply", _p(dy), _p(src_bits), _p(dym), dy.numel(), 0.2, _code(dy.dtype), _st())
+            else:
+                L.check(rc, "xmc_conv_pw1x1_masked_src")
+        return dx, dym
+    if staged is not None:
+        d.mask_bits = staged.bits.data_ptr()
+        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
+                         f"dgrad+bits {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
+            rc = L.load().xmc_conv_ptile_bits(C.byref(d), _st())
+        if rc == 0:
+            return (dx, dxp) if want_sumpool else dx
+        if rc != 1:
+            L.check(rc, "xmc_conv_ptile_bits")
+        d.mask_bits, d.src = None, staged.materialised().data_ptr()
+    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
+                     f"dgrad {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
+        _igemm(d, "xmc_conv_igemm(dgrad)")
+    return (dx, dxp) if want_sumpool else dx
+
+
+def _dgrad_desc(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=False, res_scale=1.0, alpha=None, want_sumpool=False, dot=None):
+    """the descriptor of `_conv_dgrad_raw`'s launch with its freshly allocated outputs: -> (d, dx, pooled dx | None, packed weights)"""
     _need_cuda(dy, w)
     N, OH, OW, CDy = dy.shape
     H, W = in_hw
@@ -467,34 +502,7 @@ def _conv_dgrad_raw(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=
         assert s == 1 and H % 2 == 0 and W % 2 == 0 and in_dtype == dy.dtype
         dxp = torch.empty((N, H // 2, W // 2, cs_p), dtype=in_dtype, device=dy.device)
         d.dst_pool, d.pool_scale = dxp.data_ptr(), 1.0
-    if src_bits is not None:
-        # ``src_bits`` (sign bytes in dy's layout): also return dy x LeakyReLU'(bits).  The streaming 1x1 kernels write it while they
-        # read dy (xmc_conv_pw1x1_masked_src); any other shape runs the data gradient and the mask pass separately.
-        assert k == 1 and s == 1 and not want_sumpool and src_bits.dtype == torch.uint8 and src_bits.numel() * 8 == dy.numel()
-        dym = torch.empty_like(dy)
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin,
-                         f"dgrad+srcmask {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k1s1", _nbytes(dy, wpk, dx, dym)):
-            rc = L.load().xmc_conv_pw1x1_masked_src(C.byref(d), _p(src_bits), _p(dym), 0.2, _st())
-            if rc == 1:
-                _igemm(d, "xmc_conv_igemm(dgrad)")
-                L.call("xmc_signmask_apply", _p(dy), _p(src_bits), _p(dym), dy.numel(), 0.2, _code(dy.dtype), _st())
-            else:
-                L.check(rc, "xmc_conv_pw1x1_masked_src")
-        return dx, dym
-    if staged is not None:
-        d.mask_bits = staged.bits.data_ptr()
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                         f"dgrad+bits {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
-            rc = L.load().xmc_conv_ptile_bits(C.byref(d), _st())
-        if rc == 0:
-            return (dx, dxp) if want_sumpool else dx
-        if rc != 1:
-            L.check(rc, "xmc_conv_ptile_bits")
-        d.mask_bits, d.src = None, staged.materialised().data_ptr()
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                     f"dgrad {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
-        _igemm(d, "xmc_conv_igemm(dgrad)")
-    return (dx, dxp) if want_sumpool else dx
+    return d, dx, dxp, wpk
 
 
 class _ZeroArena:
@@ -685,18 +693,52 @@ def _conv_wgrad_raw(x, dy, geom, scale=None, up=False, want_bias=False, bias_dot
         with prof.launch("wgrad_kernel (conv weight gradient, MFMA + split-K atomics)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
                          f"wgrad {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, dy, dwp)):
             L.check(L.load().xmc_conv_wgrad_bias(C.byref(d), _p(dwp), _p(gb), _st()), "xmc_conv_wgrad")
-    gw = torch.empty((geom.cout, geom.cin // geom.groups, geom.k, geom.k), dtype=torch.float32, device=x.device)
-    if want_bias:
+    return _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale, bias_dot, dot)
+
+
+def _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale=None, bias_dot=None, dot=None):
+    """the packed accumulators of a weight-gradient launch (dwp f32 [k*k, rows, CS]; gb: the bias replicas or None) -> gw [Co,Ci,k,k],
+    or (gw, bias gradient [CDy]) when gb is given"""
+    gw = torch.empty((geom.cout, geom.cin // geom.groups, geom.k, geom.k), dtype=torch.float32, device=dwp.device)
+    if gb is not None:
         assert geom.groups == 1
-        gbs = torch.empty(CDy, dtype=torch.float32, device=x.device)
+        gbs = torch.empty(CDy, dtype=torch.float32, device=dwp.device)
         assert (bias_dot is None) == (dot is None)
         L.call("xmc_unpack_wgrad_bias_dot", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
-               _p(geom.perm_dev(x.device)), 0, _p(gb), _p(gbs), CDy, _p(bias_dot), _p(dot), _st())
+               _p(geom.perm_dev(dwp.device)), 0, _p(gb), _p(gbs), CDy, _p(bias_dot), _p(dot), _st())
         return gw, gbs
     assert bias_dot is None
     L.call("xmc_unpack_wgrad_grouped", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
-           _p(geom.perm_dev(x.device)), 0, geom.groups, _st())
+           _p(geom.perm_dev(dwp.device)), 0, geom.groups, _st())
     return gw
+
+
+def _gtail_bwd_raw(dy, img, y, w, geom, want_w, want_bias, grid_cap=0):
+    """The backward of `y -> conv_out -> tanh = img` (y: conv_out's input, already through the tail's LeakyReLU) from the gradient
+    ``dy`` of img, as ONE pass over y (xmc_gtail_bwd): -> (dz, 2x2 sum pool of dz, gw | None, bias gradient | None) with
+    dz = conv_out^T(dy * tanh'(img)) * LeakyReLU'(y), or None when the kernel does not take the case -- the caller then runs
+    xmc_tanh_bwd, the weight gradient and the data gradient separately, with the same results (dz and its pool bit for bit)."""
+    N, H, W, CS = y.shape
+    if (_code(y.dtype) != L.BF16 or CS != 32 or geom.cout > 4 or geom.k != 3 or geom.s != 1 or geom.p != 1 or geom.groups != 1
+            or H % 8 or W % 2 or "no_gtail_fused" in _DEBUG_DISPATCH):
+        return None
+    _need_cuda(dy, img, y, w)
+    assert dy.shape == img.shape == (N, H, W, 8) and dy.dtype == img.dtype == y.dtype and img.is_contiguous() and y.is_contiguous()
+    d, dz, dsc, _wpk = _dgrad_desc(dy, w, geom, (H, W), y.dtype, mask=y, want_sumpool=True)
+    rows = pad_to(8, 32)
+    dwp = _arena.zeros((9, rows, CS), y.device) if want_w else None
+    gb = _arena.zeros((16, 8), y.device) if want_w and want_bias else None      # XMC_BIAS_REPLICAS
+    with prof.launch("gtail_bwd_kernel (conv_out dgrad + wgrad + tanh', one pass)", 2.0 * N * H * W * 8 * 32 * 9 * (2 if want_w else 1),
+                     f"gtail-bwd {y.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(dy, img, y, dz, dsc)):
+        rc = L.load().xmc_gtail_bwd(C.byref(d), _p(img), _p(dwp), _p(gb), rows, int(grid_cap), _st())
+    if rc == 1:
+        return None
+    L.check(rc, "xmc_gtail_bwd")
+    if not want_w:
+        return dz, dsc, None, None
+    r = _wgrad_unpack(dwp, gb, geom, rows, CS, 8)
+    gw, gbs = r if gb is not None else (r, None)
+    return dz, dsc, gw, gbs
 
 
 # ------------------------------------------------------------------------------------------ pointwise passes shared by the node modules

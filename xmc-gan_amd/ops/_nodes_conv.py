@@ -7,7 +7,7 @@ from .. import lib as L
 from ._config import _code, _p, _skip_wgrad, _st, act_dtype, pad_to
 from ._engine import (
     _affine_bwd_raw, _affine_fwd_raw, _axpby_bwd_fused, _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw,
-    _pooled_take, _upconv_dgrad_raw, _upconv_fwd_raw, _zeros_f32, _zeros_f32_out)
+    _gtail_bwd_raw, _pooled_take, _upconv_dgrad_raw, _upconv_fwd_raw, _zeros_f32, _zeros_f32_out)
 from ._nodes_leaf import CastFn, ColSumFn, MaskFn, TanhBwdFn
 
 
@@ -302,7 +302,18 @@ class GBlockEndFn(torch.autograd.Function):
             dy = dy.to(dt)
         skip_w = _skip_wgrad()
         dw_out = db_out = None
+        fused = None
         if ctx.tail:
+            # one pass over y (xmc_gtail_bwd: tanh', conv_out's weight / bias gradient and its masked, pooled data gradient); None for
+            # the shapes and modes it declines and under XMC_DEBUG_DISPATCH=no_gtail_fused: then the three launches below
+            fused = _gtail_bwd_raw(dy, img, y, w_out, geom_out, want_w=not skip_w, want_bias=ctx.has_bo)
+        if fused is not None:
+            dz, dsc, dw_out, db_out = fused
+            if dw_out is not None:
+                dw_out = dw_out.view(w_out.shape)
+            if db_out is not None:
+                db_out = db_out[: geom_out.cout]
+        elif ctx.tail:
             dpre = torch.empty_like(dy)
             L.call("xmc_tanh_bwd", _p(dy), _p(img), _p(dpre), dy.numel(), _code(dt), _st())
             if not skip_w:
