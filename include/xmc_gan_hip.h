@@ -52,7 +52,8 @@ extern "C" {
  *     xmc_fid_resize_u8 / xmc_pool3x3 / xmc_fid_moments (csrc/fid.hip);
  *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip);
  *     xmc_crop_flip_normalize (csrc/datafeed.hip);
- *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass). */
+ *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass);
+ *     xmc_caption_gather (csrc/captionfeed.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -764,6 +765,21 @@ int xmc_rprecision(const float* img, const float* txt, const int32_t* cand, int3
  * XMC_EALIGN: pool or out not 16-byte aligned, offsets not 8-byte aligned.  All refused before any launch.  No atomics. */
 int xmc_crop_flip_normalize(const uint8_t* pool, int64_t pool_bytes, const int64_t* offsets, const int32_t* hw, int N, const int32_t* params,
                             const float* table, float* out, int B, int S, void* stream);
+
+/* ---- a batch's text-encoder outputs out of device-resident tables of cached embeddings (csrc/captionfeed.hip; xmc_gan_amd/captioncache.py) --
+ * sent_tab f32 [N,E]: the sentence row of every cached caption.  tok_tab f32 [tok_rows,E]: the VALID token rows of every caption back to back,
+ * caption r's lens[r] (int32 [N]) rows starting at row tok_offsets[r] (int64 [N]).  rows int32 [B]: the captions of the batch.
+ *   words f32 [B,E,T]:  words[b][e][t] = t < lens[r] ? tok_tab[(tok_offsets[r] + t) * E + e] : 0,   r = rows[b]
+ *   sent  f32 [B,E]:    sent[b][e] = sent_tab[r * E + e]
+ *   mask  u8  [B,T]:    mask[b][t] = t >= lens[r]  (1 at padding: the bytes of a bool tensor)
+ * A transposing copy, no arithmetic on a value: bit-equal to what the encoder returned when the tables were written.
+ * The CALLER checks rows (0 <= r < N) and the index (offsets increasing by lens, inside tok_rows); whatever it is handed, the kernel reads
+ * lens / tok_offsets / sent_tab at a row clamped to [0, N), takes the length clamped to [0, T] and reads tok_tab at rows clamped to
+ * [0, tok_rows), and writes exactly B*E*T + B*E floats and B*T bytes.
+ * XMC_EINVAL: a NULL pointer, N < 1, tok_rows < 1.  XMC_ESHAPE: B < 1, E < 4, E % 4 != 0, T < 1, T > 64.
+ * XMC_EALIGN: sent_tab, tok_tab, words or sent not 16-byte aligned, tok_offsets not 8-byte aligned.  All refused before any launch.  No atomics. */
+int xmc_caption_gather(const float* sent_tab, const float* tok_tab, int64_t tok_rows, const int64_t* tok_offsets, const int32_t* lens, int N,
+                       const int32_t* rows, int B, int E, int T, float* words, float* sent, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ the crop offsets and flips.  The PIL path draws the same distributions from torc
 see the same distribution of batches, not the same batches.
 
 Out of scope: pools that do not fit in device memory (no host streaming), per-rank shards of the pool (every rank holds all of it), writing
-the engine's [N,H,W,8] layout directly, cached caption embeddings.
+the engine's [N,H,W,8] layout directly.  (Cached caption embeddings: xmc_gan_amd/captioncache.py, ``--caption_cache``.)
 """
 import collections
 import os

@@ -183,6 +183,7 @@ _SIGS = {
     "xmc_resize_bilinear_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_rprecision": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "xmc_crop_flip_normalize": [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp],
+    "xmc_caption_gather": [vp, vp, i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp],
 }
 _RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p}
 EXPORTS = tuple(_SIGS)

@@ -429,6 +429,69 @@ def crop_flip_normalize(pool, offsets, hw, params, size, out=None, table=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ a batch's text-encoder outputs from cached embeddings (csrc/captionfeed.hip)
+def validate_caption_rows(rows, n):
+    """The bound `caption_gather` needs, checked on the host array: rows int32 [B], B >= 1, every entry in [0, n).  ValueError names the
+    first offending entry."""
+    rows = np.asarray(rows)
+    if rows.ndim != 1 or rows.shape[0] < 1 or rows.dtype != np.int32:
+        raise ValueError(f"caption rows: int32 [B] with B >= 1 expected, got {rows.dtype} {rows.shape}")
+    bad = (rows < 0) | (rows >= n)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError(f"caption rows: entry {b} = {int(rows[b])} is out of range for a table of {n} captions")
+
+
+def caption_gather(sent_tab, tok_tab, tok_offsets, lens, rows, T, out=None):
+    """What a frozen text encoder returned for the captions ``rows`` when the tables were written: (words_embs f32 [B,E,T], sent_embs f32
+    [B,E], mask bool [B,T], True at padding), one launch on the current stream.  words_embs[b,e,t] = tok_tab[tok_offsets[r] + t, e] for
+    t < lens[r] and 0 beyond, sent_embs[b] = sent_tab[r], r = rows[b].
+
+    ``sent_tab`` f32 [N,E], ``tok_tab`` f32 [rows,E] (only the valid tokens, caption by caption), ``tok_offsets`` int64 [N], ``lens`` int32 [N],
+    all on the device; ``rows`` a `HostMirror` of int32 [B], or the host array (uploaded here).  The host copy is checked
+    (`validate_caption_rows`) BEFORE anything is launched; a violation, or rows that come without a host copy, is a ValueError.  ``out``: the
+    caller's three tensors.  E % 4 == 0, 1 <= T <= 64: anything else is the library's XMC_ESHAPE, raised as ValueError."""
+    N = int(lens.shape[0]) if lens.dim() == 1 else -1
+    if isinstance(rows, HostMirror):
+        validate_caption_rows(rows.host, N)
+    else:
+        if torch.is_tensor(rows):
+            if rows.device.type != "cpu":
+                raise ValueError("caption_gather: rows must come with their host copy (an ops.HostMirror or a host array): the bound is "
+                                 "checked there, without a read-back")
+            rows = rows.numpy()
+        validate_caption_rows(rows, N)
+        _need_cuda(sent_tab)
+        rows = HostMirror(rows, sent_tab.device)
+    _need_cuda(sent_tab, tok_tab, tok_offsets, lens, rows.dev)
+    T, B = int(T), rows.host.shape[0]
+    if sent_tab.dtype != torch.float32 or sent_tab.dim() != 2 or sent_tab.shape[0] != N or not sent_tab.is_contiguous():
+        raise ValueError(f"caption_gather: sent_tab must be a contiguous f32 [{N},E] tensor, got {sent_tab.dtype} {tuple(sent_tab.shape)}")
+    E = int(sent_tab.shape[1])
+    if tok_tab.dtype != torch.float32 or tok_tab.dim() != 2 or tok_tab.shape[1] != E or tok_tab.shape[0] < 1 or not tok_tab.is_contiguous():
+        raise ValueError(f"caption_gather: tok_tab must be a contiguous f32 [rows >= 1,{E}] tensor, got {tok_tab.dtype} {tuple(tok_tab.shape)}")
+    if tok_offsets.dtype != torch.int64 or tuple(tok_offsets.shape) != (N,) or not tok_offsets.is_contiguous() or lens.dtype != torch.int32 \
+            or not lens.is_contiguous():
+        raise ValueError(f"caption_gather: tok_offsets int64 [{N}] and lens int32 [{N}] expected, got {tok_offsets.dtype} "
+                         f"{tuple(tok_offsets.shape)} and {lens.dtype} {tuple(lens.shape)}")
+    if rows.dev.dtype != torch.int32 or tuple(rows.dev.shape) != (B,) or not rows.dev.is_contiguous():
+        raise ValueError("caption_gather: the device copy of rows does not match its host copy")
+    dev = sent_tab.device
+    shapes = ((B, E, T), (B, E), (B, T))
+    dtypes = (torch.float32, torch.float32, torch.bool)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    elif len(out) != 3 or any(tuple(o.shape) != s or o.dtype != d or not o.is_contiguous() or o.device != dev for o, s, d in zip(out, shapes, dtypes)):
+        raise ValueError(f"caption_gather: out must be contiguous f32 {shapes[0]}, f32 {shapes[1]} and bool {shapes[2]} tensors on {dev}")
+    words, sent, mask = out
+    rc = getattr(L.load(), "xmc_caption_gather")(_p(sent_tab), _p(tok_tab), tok_tab.shape[0], _p(tok_offsets), _p(lens), N, _p(rows.dev), B, E, T,
+                                                 _p(words), _p(sent), _p(mask), _st())
+    if rc == -3:
+        raise ValueError(f"caption_gather: XMC_ESHAPE (shape out of range): E = {E} must be a multiple of 4 and T = {T} in [1, 64]")
+    L.check(rc, "xmc_caption_gather")
+    return words, sent, mask
+
+
 # ------------------------------------------------------------------------------------------ FID evaluation (csrc/fid.hip): f32, outside autograd
 def _fid_arg(x, what, dtype, dims):
     _need_cuda(x)

@@ -144,11 +144,18 @@ class RPrecision:
 
 
 def usable_with(text_encoder, image_encoder):
-    """None when ``text_encoder``'s sentence codes live in ``image_encoder``'s space (an RNN_ENCODER of the same width), else the reason"""
+    """None when ``text_encoder``'s sentence codes live in ``image_encoder``'s space (an RNN_ENCODER of the same width, or a
+    `CachedTextEncoder` whose cache was built by one), else the reason"""
     from xmc_gan.model.encoder import RNN_ENCODER
-    if not isinstance(text_encoder, RNN_ENCODER):
+    from .captioncache import CachedTextEncoder
+    if isinstance(text_encoder, CachedTextEncoder):
+        if text_encoder.encoder_name != "RNN":
+            return f"the caption cache was built by a {text_encoder.encoder_name} encoder, the DAMSM image encoder is paired with RNN_ENCODER"
+        width = text_encoder.emb_dim
+    elif not isinstance(text_encoder, RNN_ENCODER):
         return f"the text encoder is a {type(text_encoder).__name__}, the DAMSM image encoder is paired with RNN_ENCODER"
-    width = text_encoder.nhidden * text_encoder.num_directions
+    else:
+        width = text_encoder.nhidden * text_encoder.num_directions
     if width != image_encoder.nef:
         return f"TEXT.EMBEDDING_DIM is {width}, the image encoder's nef is {image_encoder.nef}"
     return None

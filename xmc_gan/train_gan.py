@@ -93,6 +93,9 @@ def parse_args(argv=None):
     parser.add_argument('--image_cache', type=str, default='', metavar='DIR',
                         help='train and evaluate from the uint8 image cache in DIR (built by xmc_gan/image_cache.py): the resized images '
                              'stay in device memory and a batch is one crop + flip + normalise launch instead of the PIL DataLoader')
+    parser.add_argument('--caption_cache', type=str, default='', metavar='DIR',
+                        help='take the text encoder\'s outputs from the caption-embedding cache in DIR (built by xmc_gan/caption_cache.py): '
+                             'no text encoder is constructed, a batch is one gather launch over tables that stay in device memory')
     return parser.parse_args(argv)
 
 
@@ -548,8 +551,8 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
         for step, data in enumerate(batches):
             imgs, texts_lst, keys, imgs_host = data
             caps, cap_lens = texts_lst[0]
-            with torch.no_grad():
-                words_embs, sent_embs, mask = text_encoder(caps, cap_lens)
+            with torch.no_grad():       # (a CachedTextEncoder looks the batch up by its keys; an encoder encodes the captions)
+                words_embs, sent_embs, mask = text_encoder.forward_keys(keys) if hasattr(text_encoder, 'forward_keys') else text_encoder(caps, cap_lens)
             words_embs, sent_embs = words_embs.detach(), sent_embs.detach()
             if visual and fixed is None:         # the reference takes these from the loader's first batch before the loop
                 i2w = getattr(getattr(train_loader, 'dataset', None), 'i2w', None)
@@ -636,7 +639,9 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
                 torch.save(dict(num_updates=int(ema.num_updates.item()), decay=ema.decay, start=ema.start), f'{model_dir}/ema_state.pth')
             logger.info('Save models')
             if test_loader is not None:
-                eval(loader=test_loader, state_epoch=epoch, text_encoder=text_encoder, netG=netG_ema if ema is not None else netG,
+                # (--caption_cache: the test split's rows are another table; the train split's encoder carries the test split's)
+                eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder,
+                     netG=netG_ema if ema is not None else netG,
                      logger=logger, num_samples=6000,
                      save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None, writer=writer)
     flush_saves()                    # the sample grids queued for the writer thread are on disk when train() returns
@@ -733,7 +738,7 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     cnt, outs = 0, []
     for imgs, texts_lst, keys in loader:
         caps, cap_lens = texts_lst[0]
-        words_embs, sent_embs, mask = text_encoder(caps, cap_lens)
+        words_embs, sent_embs, mask = text_encoder.forward_keys(keys) if hasattr(text_encoder, 'forward_keys') else text_encoder(caps, cap_lens)
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
@@ -811,6 +816,8 @@ def main(argv=None):
         raise SystemExit(f'--diffaug: {e}')
     if args.image_cache and args.synthetic > 0:
         raise SystemExit('--image_cache and --synthetic exclude each other')
+    if args.caption_cache and args.synthetic > 0:
+        raise SystemExit('--caption_cache and --synthetic exclude each other')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -889,7 +896,23 @@ def main(argv=None):
                                                    num_workers=int(cfg.TRAIN.NUM_WORKERS), pin_memory=True)
         test_loader = torch.utils.data.DataLoader(test_set, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=False,
                                                   num_workers=int(cfg.TRAIN.NUM_WORKERS))
-    if args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':
+    if args.caption_cache:      # the encoder's outputs out of device-resident tables (xmc_gan_amd/captioncache.py): no encoder is constructed here
+        from xmc_gan_amd.captioncache import CachedTextEncoder, CaptionCache
+        cached = {}
+        for mode, loader in (('train', train_loader), ('test', test_loader)):
+            text_set = loader.dataset
+            if text_set.transform is not None:      # (the PIL loader's dataset: the same captions, read without its images)
+                text_set = data_arch(data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
+            try:
+                c_cache = CaptionCache.load(args.caption_cache, mode, cfg, text_set, ops.precision(), cfg_path=args.cfg)
+            except ValueError as e:
+                raise SystemExit(f'--caption_cache: {e}')     # (the message ends with the command that builds this split's cache)
+            cached[mode] = CachedTextEncoder(c_cache, device)
+            logger.info(f'caption cache {c_cache.f32_path}: {len(c_cache)} captions, {c_cache.nbytes} bytes on the device, {c_cache.encoder} encoder '
+                        f'{c_cache.meta["encoder_fingerprint"]} from {c_cache.meta["encoder_source"]}')
+        text_encoder = cached['train']
+        text_encoder.eval_encoder = cached['test']
+    elif args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':
         text_encoder = SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, seed, device)
     elif cfg.TEXT.ENCODER_NAME == 'SBERT':
         # frozen weights read from the model directory, the same on every rank: no state dict to load (TEXT.ENCODER_DIR is '' in every
