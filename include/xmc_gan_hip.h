@@ -53,7 +53,8 @@ extern "C" {
  *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip);
  *     xmc_crop_flip_normalize (csrc/datafeed.hip);
  *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass);
- *     xmc_caption_gather (csrc/captionfeed.hip). */
+ *     xmc_caption_gather (csrc/captionfeed.hip);
+ *     xmc_manifold_slices / xmc_row_sqnorm / xmc_knn_radius2 / xmc_manifold_count (csrc/manifold.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -780,6 +781,30 @@ int xmc_crop_flip_normalize(const uint8_t* pool, int64_t pool_bytes, const int64
  * XMC_EALIGN: sent_tab, tok_tab, words or sent not 16-byte aligned, tok_offsets not 8-byte aligned.  All refused before any launch.  No atomics. */
 int xmc_caption_gather(const float* sent_tab, const float* tok_tab, int64_t tok_rows, const int64_t* tok_offsets, const int32_t* lens, int N,
                        const int32_t* rows, int B, int E, int T, float* words, float* sent, uint8_t* mask, void* stream);
+
+/* ---- precision / recall / density / coverage: k-nearest-neighbour statistics of feature rows (csrc/manifold.hip; xmc_gan_amd/manifold.py) ----
+ * All f32, in both builds.  d2(a, b) = max(|a|^2 + |b|^2 - 2 a.b, 0); the dot products run on the f32-input MFMA as ONE chain over D in a
+ * fixed order of the columns (no split over D), so a pair's d2 has the same bits whatever the grid.  The N x N matrix exists nowhere: the
+ * k-th-neighbour, membership and nearest-distance reductions sit in the matrix kernel's epilogue, one query per lane.  The candidate rows are
+ * split into `slices` ranges of whole 128-row chunks, one workgroup per (128 queries, slice); with more than one slice every slice writes
+ * its partial k-lists / counts / minima into `ws` and a second launch merges them.  The k smallest of a union, integer sums and minima do
+ * not depend on the order of merging and there are no atomics: the outputs are the same bytes for every `slices` and from run to run.
+ *   slices: what a call with (Nq query rows, Nc candidate rows, slices) really uses: slices == 0 (the library chooses: as many as keep the grid
+ *           within one round of resident workgroups, 512 / ceil(Nq / 128)) or the request, clamped to [1, min(ceil(Nc / 128), 64)].  Host only.  0 when Nq < 1 or Nc < 1.
+ *   row_sqnorm: n2[i] = |x_i|^2 of x f32 [N,D]: one wave per row, a lane's elements in order, then the fixed xor butterfly over the wave.
+ *   knn_radius2: r2[i] = the k-th smallest d2(x_i, x_j) over j != i (the row is excluded by INDEX; duplicates count as separate
+ *           neighbours).  n2 = row_sqnorm(x).  ws: S * N * k floats, S = slices(N, N, slices); may be NULL when S == 1.
+ *   manifold_count: for every row i of a [Na,D] against the rows of b [Nb,D] (na2, nb2 their squared norms):
+ *           count[i] = #{ j : d2(a_i, b_j) <= rb2[j] } (int32) and near2[i] = min_j d2(a_i, b_j).  rb2 == NULL: only near2 is written
+ *           (count may be NULL then); near2 may be NULL.  ws: S * Na * 8 bytes, S = slices(Na, Nb, slices); may be NULL when S == 1.
+ * XMC_EINVAL: a required pointer NULL (rb2 and near2 both NULL; count NULL with rb2 given; ws NULL or ws_bytes too small with S > 1),
+ * N / Na / Nb < 1, k outside [1, 16], slices < 0.  XMC_ESHAPE: D % 4 != 0, D < 4, D > 4096, N < k + 1, more than 2^30 rows.
+ * XMC_EALIGN: a float pointer not 16-byte aligned (count: 4).  All refused before any launch. */
+int xmc_manifold_slices(int Nq, int Nc, int slices);
+int xmc_row_sqnorm(const float* x, float* n2, int N, int D, void* stream);
+int xmc_knn_radius2(const float* x, const float* n2, float* r2, float* ws, int64_t ws_bytes, int N, int D, int k, int slices, void* stream);
+int xmc_manifold_count(const float* a, const float* na2, const float* b, const float* nb2, const float* rb2, int32_t* count, float* near2,
+                       void* ws, int64_t ws_bytes, int Na, int Nb, int D, int slices, void* stream);
 
 #ifdef __cplusplus
 }

@@ -345,9 +345,9 @@ def _read_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def stats_of_dir(directory, extractor, batch=100):
-    """`FeatureStats` of the PNG / JPEG files of ``directory`` in sorted order, ``batch`` files at a time: decoded by PIL on up to 8 host
-    threads; the files of a batch that share a size go through the front end together"""
+def features_of_dir(directory, extractor, batch=100):
+    """the feature rows of the PNG / JPEG files of ``directory`` in sorted order, one tensor per group of same-sized files of ``batch`` files:
+    decoded by PIL on up to 8 host threads; the files of a batch that share a size go through the front end together"""
     from concurrent.futures import ThreadPoolExecutor
     files = list_images(directory)
     if not files:
@@ -356,14 +356,20 @@ def stats_of_dir(directory, extractor, batch=100):
         cores = len(os.sched_getaffinity(0))
     except AttributeError:
         cores = os.cpu_count() or 1
-    st = FeatureStats(DIMS, extractor.device)
     with ThreadPoolExecutor(max(1, min(8, cores))) as pool:
         for i in range(0, len(files), batch):
             groups = {}
             for arr in pool.map(_read_rgb, files[i:i + batch]):
                 groups.setdefault(arr.shape, []).append(arr)
             for arrs in groups.values():
-                st.update(extractor(torch.from_numpy(np.stack(arrs))))
+                yield extractor(torch.from_numpy(np.stack(arrs)))
+
+
+def stats_of_dir(directory, extractor, batch=100):
+    """`FeatureStats` of the image files of ``directory`` (`features_of_dir`)"""
+    st = FeatureStats(DIMS, extractor.device)
+    for feats in features_of_dir(directory, extractor, batch):
+        st.update(feats)
     return st
 
 

@@ -184,6 +184,10 @@ _SIGS = {
     "xmc_rprecision": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "xmc_crop_flip_normalize": [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp],
     "xmc_caption_gather": [vp, vp, i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp],
+    "xmc_manifold_slices": [i32, i32, i32],
+    "xmc_row_sqnorm": [vp, vp, i32, i32, vp],
+    "xmc_knn_radius2": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "xmc_manifold_count": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
 }
 _RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p}
 EXPORTS = tuple(_SIGS)

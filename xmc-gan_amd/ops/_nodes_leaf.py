@@ -587,6 +587,66 @@ def rprecision(img, txt, cand, return_scores=False):
     return (rank, score) if return_scores else rank
 
 
+# ------------------------------------------------------------------------------------------ precision / recall / density / coverage (csrc/manifold.hip): f32, outside autograd
+def _manifold_dims(what, *xs):
+    D = xs[0].shape[1]
+    if any(x.shape[1] != D or x.shape[0] < 1 or x.device != xs[0].device for x in xs) or D < 4 or D % 4 or D > 4096:
+        raise ValueError(f"{what}: f32 [N,D] rows on one device with D % 4 == 0 and 4 <= D <= 4096 expected, got {[tuple(x.shape) for x in xs]}")
+    return D
+
+
+def _manifold_slices(what, nq, nc, slices):
+    slices = int(slices)
+    if slices < 0:
+        raise ValueError(f"{what}: slices = {slices}")
+    return getattr(L.load(), "xmc_manifold_slices")(nq, nc, slices)
+
+
+def row_sqnorm(x):
+    """|x_i|^2 of the rows of x f32 [N,D] (D % 4 == 0, D <= 4096) -> f32 [N], summed in a fixed order"""
+    x = _fid_arg(x, "row_sqnorm", torch.float32, 2)
+    D = _manifold_dims("row_sqnorm", x)
+    n2 = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    L.call("xmc_row_sqnorm", _p(x), _p(n2), x.shape[0], D, _st())
+    return n2
+
+
+def knn_radius2(x, k, slices=0):
+    """rad2 f32 [N]: the k-th smallest squared distance from row i of x f32 [N,D] to the OTHER rows (excluded by index; duplicates are
+    neighbours at distance 0).  1 <= k <= 16, N >= k + 1.  ``slices``: ranges the candidate rows are split into (0: the library
+    chooses); the result is the same bytes for every value."""
+    x = _fid_arg(x, "knn_radius2", torch.float32, 2)
+    D, N, k = _manifold_dims("knn_radius2", x), x.shape[0], int(k)
+    if not 1 <= k <= 16 or N < k + 1:
+        raise ValueError(f"knn_radius2: k = {k} with {N} rows; 1 <= k <= 16 and N >= k + 1 expected")
+    S = _manifold_slices("knn_radius2", N, N, slices)
+    n2 = row_sqnorm(x)
+    r2 = torch.empty((N,), dtype=torch.float32, device=x.device)
+    ws = torch.empty((S * N * k,), dtype=torch.float32, device=x.device) if S > 1 else None
+    L.call("xmc_knn_radius2", _p(x), _p(n2), _p(r2), _p(ws), 0 if ws is None else ws.numel() * 4, N, D, k, S, _st())
+    return r2
+
+
+def manifold_count(a, b, rb2, slices=0):
+    """For every row i of a f32 [Na,D] against the rows of b f32 [Nb,D]: count int32 [Na] = the number of rows j of b with
+    |a_i - b_j|^2 <= rb2[j] (rb2 f32 [Nb], e.g. `knn_radius2(b, k)`), and near2 f32 [Na] = min_j |a_i - b_j|^2.  ``rb2`` None: count is
+    None and only near2 is computed.  Returns (count, near2); the same bytes for every ``slices``."""
+    a, b = _fid_arg(a, "manifold_count", torch.float32, 2), _fid_arg(b, "manifold_count", torch.float32, 2)
+    D, Na, Nb = _manifold_dims("manifold_count", a, b), a.shape[0], b.shape[0]
+    if rb2 is not None:
+        rb2 = _fid_arg(rb2, "manifold_count", torch.float32, 1)
+        if rb2.shape[0] != Nb or rb2.device != a.device:
+            raise ValueError(f"manifold_count: rb2 {tuple(rb2.shape)} on {rb2.device}, f32 [{Nb}] on {a.device} expected")
+    S = _manifold_slices("manifold_count", Na, Nb, slices)
+    na2, nb2 = row_sqnorm(a), row_sqnorm(b)
+    count = torch.empty((Na,), dtype=torch.int32, device=a.device) if rb2 is not None else None
+    near2 = torch.empty((Na,), dtype=torch.float32, device=a.device)
+    ws = torch.empty((S * Na * 2,), dtype=torch.float32, device=a.device) if S > 1 else None
+    L.call("xmc_manifold_count", _p(a), _p(na2), _p(b), _p(nb2), _p(rb2), _p(count), _p(near2), _p(ws), 0 if ws is None else ws.numel() * 4,
+           Na, Nb, D, S, _st())
+    return count, near2
+
+
 # ------------------------------------------------------------------------------------------ differentiable augmentation
 def _diffaug_raw(x, params, cut, color, channels, transposed, linear_only):
     """one sums launch (only with a colour component) and one apply launch of csrc/augment.hip"""

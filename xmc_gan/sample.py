@@ -3,7 +3,8 @@
     python xmc_gan/sample.py --cfg xmc_gan/cfg/<preset>.yml --checkpoint <netG_*.pth | netG_ema_*.pth> --out DIR
                              (--captions FILE | --token_ids FILE.npy | --synthetic N) [--n_per_caption K --seed S --truncation PSI]
                              [--best_of M --netD netD_*.pth] [--walk N] [--interp_sent N] [--grid_max N] [--no_png]
-                             [--fid_against DIR_OR_NPZ --fid_inception PATH] [--rprecision --damsm_image_encoder PATH]
+                             [--fid_against DIR_OR_NPZ --fid_inception PATH] [--prdc_against DIR_OR_FEATURES_NPZ [--prdc_k K]]
+                             [--rprecision --damsm_image_encoder PATH]
 
 Writes ``<out>/<caption index:05d>_<k>.png`` (K images per caption), ``<out>/grid.png`` (the first ``--grid_max`` of them, every image min-max scaled
 on its own like the trainer's sample grids), ``<out>/captions.txt`` and ``<out>/manifest.json``.  The generator runs on the HIP kernels of
@@ -61,6 +62,10 @@ def parse_args(argv=None):
                         help='score the sampled images: FID against an image directory or an .npz statistics file -> manifest "fid"')
     parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
                         help='FID Inception weights for --fid_against (the pt_inception-2015-12-05-*.pth state dict; default: $XMC_FID_INCEPTION)')
+    parser.add_argument('--prdc_against', type=str, default='', metavar='DIR_OR_FEATURES_NPZ',
+                        help='score the sampled images: precision / recall / density / coverage against an image directory or an .npz feature '
+                             'file (xmc_gan/prdc.py --save_features) -> manifest "prdc"; takes --fid_inception')
+    parser.add_argument('--prdc_k', type=int, default=5, metavar='K', help='--prdc_against: nearest neighbours (1..16)')
     parser.add_argument('--rprecision', action='store_true',
                         help='score the sampled images: R-precision against their captions (RNN presets) -> manifest "r_precision"')
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
@@ -104,6 +109,14 @@ def _check_args(args):
             raise SystemExit(f'--fid_against: {args.fid_against} is neither an image directory nor an .npz statistics file')
         if not args.fid_inception or not os.path.isfile(args.fid_inception):
             raise SystemExit(f'--fid_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
+    if args.prdc_against:
+        args.fid_inception = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
+        if not (os.path.isdir(args.prdc_against) or (os.path.isfile(args.prdc_against) and args.prdc_against.endswith('.npz'))):
+            raise SystemExit(f'--prdc_against: {args.prdc_against} is neither an image directory nor an .npz feature file')
+        if not 1 <= args.prdc_k <= 16:
+            raise SystemExit(f'--prdc_k: {args.prdc_k}; 1 <= K <= 16 expected')
+        if not args.fid_inception or not os.path.isfile(args.fid_inception):
+            raise SystemExit(f'--prdc_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
     if args.rprecision:
         args.damsm_image_encoder = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
         if not args.damsm_image_encoder or not os.path.isfile(args.damsm_image_encoder):
@@ -242,6 +255,12 @@ def main(argv=None):
         from xmc_gan.utils.visual import fid_extractor
         from xmc_gan_amd.fid import FeatureStats, frechet_distance, stats_of
         fid_ex, fid_stats = fid_extractor(args.fid_inception, device), FeatureStats(device=device)
+    prdc_bank = None
+    if args.prdc_against:                                            # the same extractor (and the same pass) as --fid_against when both are given
+        from xmc_gan.utils.visual import fid_extractor
+        from xmc_gan_amd import manifold as MF
+        fid_ex = fid_ex or fid_extractor(args.fid_inception, device)
+        prdc_bank = MF.FeatureBank(device=device)
     rp = rp_enc = None
     if args.rprecision:
         from xmc_gan_amd import rprecision as RP
@@ -268,8 +287,12 @@ def main(argv=None):
                 u8, sc = ops.image_to_u8(x8), None
             if c0 * K < n_grid:
                 kept[c0 * K:min(n_grid, c1 * K)] = x8[:n_grid - c0 * K]
-            if fid_stats is not None:
-                fid_stats.update(fid_ex(u8))
+            if fid_ex is not None:
+                feats = fid_ex(u8)
+                if fid_stats is not None:
+                    fid_stats.update(feats)
+                if prdc_bank is not None:
+                    prdc_bank.update(feats)
             if rp is not None:                                       # image r of the batch was made from caption r // K
                 rp.update(rp_enc.encode_u8(u8)[1], sents[c0:c1], torch.arange(nc).repeat_interleave(K))
             host = u8.cpu().numpy()                                  # one copy per batch: 3 bytes per pixel
@@ -311,6 +334,14 @@ def main(argv=None):
             raise SystemExit('--fid_against: a covariance needs at least two sampled images')
         fid = frechet_distance(*stats_of(args.fid_against, fid_ex, bs), *fid_stats.finalize())
         print(f'FID: {fid}')
+    prdc = None
+    if prdc_bank is not None:
+        try:
+            prdc = MF.prdc(MF.bank_of(args.prdc_against, fid_ex, bs, device), prdc_bank, args.prdc_k)
+        except ValueError as e:
+            raise SystemExit(f'--prdc_against: {e}')
+        print(f'precision: {prdc["precision"]} recall: {prdc["recall"]} density: {prdc["density"]} coverage: {prdc["coverage"]} '
+              f'(k={prdc["k"]}, n={prdc["n_real"]}/{prdc["n_fake"]})')
     r_precision = None
     if rp is not None:
         try:
@@ -324,6 +355,8 @@ def main(argv=None):
                     captions=n, fid=fid, grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
     if rp is not None:                                               # (only with --rprecision: the manifest of every other run is unchanged)
         manifest['r_precision'] = r_precision
+    if prdc is not None:                                             # (only with --prdc_against)
+        manifest['prdc'] = prdc
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

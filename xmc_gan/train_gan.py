@@ -81,6 +81,9 @@ def parse_args(argv=None):
     parser.add_argument('--fid_inception', type=str, default='', metavar='PATH',
                         help="FID Inception weights (the pt_inception-2015-12-05-*.pth state dict of pytorch_fid): eval() scores on this "
                              "project's kernels (default: $XMC_FID_INCEPTION; without either, pytorch_fid if it is installed)")
+    parser.add_argument('--prdc', type=int, default=0, metavar='K',
+                        help='> 0: eval() also reports improved precision / recall and density / coverage with K nearest neighbours (typical: '
+                             '5), from the Inception features it extracts for FID (needs --fid_inception or XMC_FID_INCEPTION).  0 (default): off')
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
                         help="DAMSM image encoder weights (image_encoder100.pth of AttnGAN's DAMSM archive): eval() also reports R-precision "
                              "(RNN presets; default: $XMC_DAMSM_IMAGE_ENCODER; without either, no R-precision)")
@@ -662,6 +665,7 @@ def _detached(last):
 _FID_INCEPTION = ['']        # --fid_inception (main()); eval() falls back to $XMC_FID_INCEPTION
 
 
+_PRDC_K = [0]                # --prdc (main())
 _DAMSM_IMAGE_ENCODER = ['']  # --damsm_image_encoder (main()); eval() falls back to $XMC_DAMSM_IMAGE_ENCODER
 _damsm_cache = {}
 
@@ -682,6 +686,17 @@ def _fid_u8(images_nchw, device):
     return nchw_to_u8(images_nchw.to(device))
 
 
+def _real_bank(loader, extractor, device, limit):
+    """feature rows of the loader's real images alone (the cached ones were made for another number of samples)"""
+    from xmc_gan_amd.manifold import FeatureBank
+    bank = FeatureBank(device=device)
+    for imgs, _, _ in loader:
+        bank.update(extractor(_fid_u8(imgs, device)))
+        if bank.n >= limit:
+            break
+    return bank
+
+
 def _real_stats(loader, extractor, device, limit):
     """statistics of the loader's real images alone (the cached ones were made for another number of samples)"""
     from xmc_gan_amd.fid import FeatureStats
@@ -695,7 +710,7 @@ def _real_stats(loader, extractor, device, limit):
 
 @torch.no_grad()
 def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
-         damsm_image_encoder=None, metrics=None):
+         damsm_image_encoder=None, metrics=None, prdc=None):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to
     ``save_dir/<key>.png`` and, unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``,
     as 8-bit PNGs of (x + 1) * 127.5.  FID (logged and written to the scalar log as 'FID'):
@@ -706,6 +721,11 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     --damsm_image_encoder, then $XMC_DAMSM_IMAGE_ENCODER), the DAMSM image encoder's weights -- the same bytes go through
     ``CNN_ENCODER.encode_u8`` and are paired with the loop's ``sent_embs`` (k = 100 candidates, 10 splits; xmc_gan_amd/rprecision.py).  Only
     with an ``RNN_ENCODER`` of the image encoder's width; otherwise one line says why it was not computed.
+    Precision / recall / density / coverage (logged, written as 'precision', 'recall', 'density', 'coverage', and put into ``metrics`` with
+    'prdc_k', 'n_real', 'n_fake'): with ``prdc`` = K > 0 (default: --prdc) and the FID extractor -- the feature batches FID takes also go into two
+    ``FeatureBank``s (xmc_gan_amd/manifold.py); the real rows are cached beside ``org_stats.npz`` as ``org_features.npz`` (reused while the
+    row count matches).  Without the Inception weights one line says why nothing was computed.  FID's value and line are what they are
+    without it.
     Returns (uint8 tensor of the generated images, FID or None)."""
     from PIL import Image
     netG.eval()
@@ -727,6 +747,21 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
             cached = load_stats(cache, with_count=True)
         if cached is None:
             real_stats = FeatureStats(device=device)
+    prdc_k = int(_PRDC_K[0] if prdc is None else prdc)
+    gen_bank = real_bank = bank_cache = prdc_why = None
+    if prdc_k > 0 and extractor is None:
+        prdc_why = 'it takes the Inception features of FID: --fid_inception PATH or XMC_FID_INCEPTION'
+    elif prdc_k > 0:
+        from xmc_gan_amd import manifold as MF
+        gen_bank = MF.FeatureBank(device=device)
+        bank_cache = os.path.join(os.path.dirname(os.path.abspath(org_dir)), 'org_features.npz') if org_dir else None
+        cached_bank = None
+        if bank_cache and os.path.isfile(bank_cache):
+            try:
+                cached_bank = MF.FeatureBank.load(bank_cache, device)
+            except ValueError:
+                cached_bank = None
+        real_bank = MF.FeatureBank(device=device) if cached_bank is None else None
     damsm = damsm_image_encoder or _DAMSM_IMAGE_ENCODER[0] or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
     image_encoder = rprec = rprec_why = None
     if damsm:
@@ -746,9 +781,16 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         if rprec is not None:
             rprec.update(image_encoder.encode_u8(fake_u8)[1], sent_embs)
         if extractor is not None:
-            gen_stats.update(extractor(fake_u8))
-            if real_stats is not None:
-                real_stats.update(extractor(_fid_u8(imgs, device)))
+            feats = extractor(fake_u8)
+            gen_stats.update(feats)
+            if gen_bank is not None:
+                gen_bank.update(feats)
+            if real_stats is not None or real_bank is not None:
+                feats = extractor(_fid_u8(imgs, device))
+                if real_stats is not None:
+                    real_stats.update(feats)
+                if real_bank is not None:
+                    real_bank.update(feats)
         for j in range(fake.size(0)):
             if save_dir:
                 Image.fromarray(to_uint8_hwc(fake[j])).save(f'{save_dir}/{keys[j]}.png')
@@ -777,6 +819,28 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         logger.info(f' epoch {state_epoch}, FID : {fid}')
         if writer is not None:
             writer.add_scalar('FID', fid, state_epoch)
+    if gen_bank is not None:
+        if real_bank is None and cached_bank.n == cnt:
+            real_bank = cached_bank
+        else:
+            if real_bank is None:             # a cache for another number of samples
+                real_bank = _real_bank(loader, extractor, device, cnt)
+            if bank_cache and real_bank.n:
+                real_bank.save(bank_cache)
+        try:
+            r = MF.prdc(real_bank, gen_bank, prdc_k)
+        except ValueError as e:
+            r, prdc_why = None, str(e)
+        if r is not None:
+            logger.info(f' epoch {state_epoch}, precision : {r["precision"]} recall : {r["recall"]} density : {r["density"]} '
+                        f'coverage : {r["coverage"]} (k={r["k"]}, n={r["n_real"]}/{r["n_fake"]})')
+            for name in ('precision', 'recall', 'density', 'coverage'):
+                if writer is not None:
+                    writer.add_scalar(name, r[name], state_epoch)
+            if metrics is not None:
+                metrics.update({name: r[name] for name in ('precision', 'recall', 'density', 'coverage', 'n_real', 'n_fake')}, prdc_k=r['k'])
+    if prdc_why is not None:
+        logger.info(f' epoch {state_epoch}, precision / recall / density / coverage not computed: {prdc_why}')
     if rprec is not None:
         try:
             r = rprec.finalize()
@@ -830,6 +894,9 @@ def main(argv=None):
     _FID_INCEPTION[0] = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
     if _FID_INCEPTION[0] and not os.path.isfile(_FID_INCEPTION[0]):
         raise SystemExit(f'--fid_inception: {_FID_INCEPTION[0]} is not a file')
+    if not 0 <= args.prdc <= 16:
+        raise SystemExit('--prdc K: 0 (off) or 1 <= K <= 16 nearest neighbours')
+    _PRDC_K[0] = args.prdc
     _DAMSM_IMAGE_ENCODER[0] = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
     if _DAMSM_IMAGE_ENCODER[0] and not os.path.isfile(_DAMSM_IMAGE_ENCODER[0]):
         raise SystemExit(f'--damsm_image_encoder: {_DAMSM_IMAGE_ENCODER[0]} is not a file')
