@@ -319,11 +319,11 @@ def frechet_distance(mu1, sigma1, mu2, sigma2):
     return float(diff @ diff + np.trace(s1) + np.trace(s2) - 2.0 * roots.sum())
 
 
-def _stats_of_batches(batches, extractor, dims=DIMS):
-    st = FeatureStats(dims, extractor.device)
-    for u8 in batches:
-        st.update(extractor(u8))
-    return st
+def accumulate(acc, feature_batches):
+    """``acc`` (a `FeatureStats`, a `manifold.FeatureBank`) after one update per batch of feature rows"""
+    for feats in feature_batches:
+        acc.update(feats)
+    return acc
 
 
 def fid_from_images(images_a, images_b, extractor, batch=100):
@@ -331,7 +331,7 @@ def fid_from_images(images_a, images_b, extractor, batch=100):
     sets = []
     for im in (images_a, images_b):
         im = torch.as_tensor(im)
-        sets.append(_stats_of_batches((im[i:i + batch] for i in range(0, im.shape[0], batch)), extractor).finalize())
+        sets.append(accumulate(FeatureStats(DIMS, extractor.device), (extractor(im[i:i + batch]) for i in range(0, im.shape[0], batch))).finalize())
     return frechet_distance(*sets[0], *sets[1])
 
 
@@ -345,13 +345,10 @@ def _read_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def features_of_dir(directory, extractor, batch=100):
-    """the feature rows of the PNG / JPEG files of ``directory`` in sorted order, one tensor per group of same-sized files of ``batch`` files:
-    decoded by PIL on up to 8 host threads; the files of a batch that share a size go through the front end together"""
+def decoded_batches(files, batch=100):
+    """the image files ``files``, ``batch`` at a time, as (their indices into ``files``, uint8 tensor [n,H,W,3]): decoded by PIL on up to 8
+    host threads (no more than the process may run on); the files of a batch that share a size come together"""
     from concurrent.futures import ThreadPoolExecutor
-    files = list_images(directory)
-    if not files:
-        raise ValueError(f"{directory} holds no image ({', '.join(IMAGE_EXTENSIONS)})")
     try:
         cores = len(os.sched_getaffinity(0))
     except AttributeError:
@@ -359,18 +356,24 @@ def features_of_dir(directory, extractor, batch=100):
     with ThreadPoolExecutor(max(1, min(8, cores))) as pool:
         for i in range(0, len(files), batch):
             groups = {}
-            for arr in pool.map(_read_rgb, files[i:i + batch]):
-                groups.setdefault(arr.shape, []).append(arr)
-            for arrs in groups.values():
-                yield extractor(torch.from_numpy(np.stack(arrs)))
+            for j, arr in enumerate(pool.map(_read_rgb, files[i:i + batch])):
+                groups.setdefault(arr.shape, []).append((i + j, arr))
+            for members in groups.values():
+                yield [m[0] for m in members], torch.from_numpy(np.stack([m[1] for m in members]))
+
+
+def features_of_dir(directory, extractor, batch=100):
+    """the feature rows of the PNG / JPEG files of ``directory`` in sorted order, one tensor per group `decoded_batches` makes of them"""
+    files = list_images(directory)
+    if not files:
+        raise ValueError(f"{directory} holds no image ({', '.join(IMAGE_EXTENSIONS)})")
+    for _, u8 in decoded_batches(files, batch):
+        yield extractor(u8)
 
 
 def stats_of_dir(directory, extractor, batch=100):
     """`FeatureStats` of the image files of ``directory`` (`features_of_dir`)"""
-    st = FeatureStats(DIMS, extractor.device)
-    for feats in features_of_dir(directory, extractor, batch):
-        st.update(feats)
-    return st
+    return accumulate(FeatureStats(DIMS, extractor.device), features_of_dir(directory, extractor, batch))
 
 
 def stats_of(path, extractor, batch=100):

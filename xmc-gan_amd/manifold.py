@@ -124,11 +124,8 @@ def prdc(real, fake, k=5):
 
 def bank_of_dir(directory, extractor, batch=100):
     """`FeatureBank` of the image files of ``directory`` in sorted order (`xmc_gan_amd.fid.features_of_dir`)"""
-    from .fid import features_of_dir
-    bank = FeatureBank(DIMS, extractor.device)
-    for feats in features_of_dir(directory, extractor, batch):
-        bank.update(feats)
-    return bank
+    from .fid import accumulate, features_of_dir
+    return accumulate(FeatureBank(DIMS, extractor.device), features_of_dir(directory, extractor, batch))
 
 
 def bank_of(path, extractor, batch=100, device="cuda"):

@@ -31,24 +31,21 @@ def parse_args(argv=None):
 
 def _check_args(args):
     """everything that can be refused before a device is touched; -> whether a directory has to be scored"""
+    from xmc_gan_amd.evaluate import image_set_kind, resolve_weights
     from xmc_gan_amd.fid import list_images
     if args.batch < 1:
         raise SystemExit('--batch must be >= 1')
     need = False
     for p in (args.a, args.b):
-        if os.path.isdir(p):
+        kind = image_set_kind(p)
+        if kind is None:
+            raise SystemExit(f'{p} is neither an image directory nor an .npz statistics file')
+        if kind == 'dir':
             if len(list_images(p)) < 2:
                 raise SystemExit(f'{p} holds fewer than two images (.png / .jpg / .jpeg): nothing to score')
             need = True
-        elif not (os.path.isfile(p) and p.endswith('.npz')):
-            raise SystemExit(f'{p} is neither an image directory nor an .npz statistics file')
     if need:
-        w = args.inception or os.environ.get('XMC_FID_INCEPTION', '')
-        if not w:
-            raise SystemExit('scoring a directory needs the FID Inception weights: --inception PATH or XMC_FID_INCEPTION')
-        if not os.path.isfile(w):
-            raise SystemExit(f'--inception: {w} is not a file')
-        args.inception = w
+        args.inception = resolve_weights(args.inception, 'XMC_FID_INCEPTION', '--inception')
     return need
 
 

@@ -24,7 +24,6 @@ import os
 import torch
 import torch.nn as nn
 
-from xmc_gan_amd import fid as _fid
 from xmc_gan_amd import lib as _L
 from xmc_gan_amd import ops
 
@@ -327,10 +326,10 @@ class SBERT_ENCODER(nn.Module):
 class _BasicConv2d(nn.Module):
     """torchvision's BasicConv2d as a parameter container: conv without bias, BatchNorm with eps 1e-3"""
 
-    def __init__(self, cin, cout, k, s, p):
+    def __init__(self, cin, cout, k, s, p, eps):
         super(_BasicConv2d, self).__init__()
         self.conv = nn.Conv2d(cin, cout, kernel_size=k, stride=s, padding=p, bias=False)
-        self.bn = nn.BatchNorm2d(cout, eps=_fid.BN_EPS)
+        self.bn = nn.BatchNorm2d(cout, eps=eps)
 
 
 class CNN_ENCODER(nn.Module):
@@ -342,6 +341,7 @@ class CNN_ENCODER(nn.Module):
     ``resize_to``: 299 as upstream; None feeds the images at their own size (at least 75x75; the tests' small maps)."""
 
     def __init__(self, nef, resize_to=299):
+        from xmc_gan_amd import fid as _fid        # (here, not at the top: a run without an image encoder imports no Inception code)
         super(CNN_ENCODER, self).__init__()
         self.nef = int(nef)
         self.resize_to = resize_to
@@ -352,7 +352,7 @@ class CNN_ENCODER(nn.Module):
                 if not hasattr(parent, part):
                     parent.add_module(part, nn.Module())
                 parent = getattr(parent, part)
-            parent.add_module(leaf, _BasicConv2d(cin, cout, k, s, p))
+            parent.add_module(leaf, _BasicConv2d(cin, cout, k, s, p, _fid.BN_EPS))
         self.emb_features = nn.Conv2d(768, self.nef, kernel_size=1, stride=1, padding=0, bias=False)      # AttnGAN's conv1x1
         self.emb_cnn_code = nn.Linear(2048, self.nef)
         initrange = 0.1                                                                                   # AttnGAN's init_trainable_weights
@@ -383,6 +383,7 @@ class CNN_ENCODER(nn.Module):
         sd = {k: v for k, v in self.state_dict(keep_vars=True).items() if v.is_floating_point()}
         key = tuple((v.data_ptr(), v._version) for v in sd.values())
         if self._folded is None or self._folded[0] != key:
+            from xmc_gan_amd import fid as _fid
             dev = self.emb_cnn_code.weight.device
             trunk = _fid.InceptionTrunk(_fid.check_inception_state(sd, "CNN_ENCODER", "the module"), dev, "torchvision")
             frozen = lambda t: nn.Parameter(t.detach().to(dev, torch.float32).contiguous(), requires_grad=False)      # noqa: E731

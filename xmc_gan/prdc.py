@@ -33,6 +33,7 @@ def parse_args(argv=None):
 
 def _check_args(args):
     """everything that can be refused before a device is touched; -> whether a directory has to be scored"""
+    from xmc_gan_amd.evaluate import image_set_kind, resolve_weights
     from xmc_gan_amd.fid import list_images
     from xmc_gan_amd.manifold import load_features
     if args.batch < 1:
@@ -41,26 +42,22 @@ def _check_args(args):
         raise SystemExit(f'--k: {args.k}; 1 <= k <= 16 expected')
     need = False
     for p in (args.a, args.b):
-        if os.path.isdir(p):
+        kind = image_set_kind(p)
+        if kind is None:
+            raise SystemExit(f'{p} is neither an image directory nor an .npz feature file')
+        if kind == 'dir':
             if len(list_images(p)) < args.k + 1:
                 raise SystemExit(f'{p} holds fewer than k + 1 = {args.k + 1} images (.png / .jpg / .jpeg): no k-th neighbour')
             need = True
-        elif os.path.isfile(p) and p.endswith('.npz'):
+        else:
             try:
                 rows = load_features(p).shape[0]
             except ValueError as e:
                 raise SystemExit(str(e))
             if rows < args.k + 1:
                 raise SystemExit(f'{p} holds {rows} rows, fewer than k + 1 = {args.k + 1}: no k-th neighbour')
-        else:
-            raise SystemExit(f'{p} is neither an image directory nor an .npz feature file')
     if need:
-        w = args.inception or os.environ.get('XMC_FID_INCEPTION', '')
-        if not w:
-            raise SystemExit('scoring a directory needs the FID Inception weights: --inception PATH or XMC_FID_INCEPTION')
-        if not os.path.isfile(w):
-            raise SystemExit(f'--inception: {w} is not a file')
-        args.inception = w
+        args.inception = resolve_weights(args.inception, 'XMC_FID_INCEPTION', '--inception')
     return need
 
 

@@ -43,6 +43,7 @@ def parse_args(argv=None):
 def _check_args(args):
     """everything that can be refused before a device is touched; -> the sorted image files"""
     from xmc_gan.config.gan import cfg, cfg_from_file
+    from xmc_gan_amd.evaluate import resolve_weights
     from xmc_gan_amd.fid import list_images
     if bool(args.captions) == bool(args.token_ids):
         raise SystemExit('give exactly one caption source: --captions FILE or --token_ids FILE')
@@ -53,9 +54,7 @@ def _check_args(args):
     files = list_images(args.images)
     if not files:
         raise SystemExit(f'{args.images} holds no image (.png / .jpg / .jpeg)')
-    args.image_encoder = args.image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
-    if not args.image_encoder or not os.path.isfile(args.image_encoder):
-        raise SystemExit(f'the DAMSM image encoder weights are needed: --image_encoder PATH or XMC_DAMSM_IMAGE_ENCODER (got {args.image_encoder!r})')
+    args.image_encoder = resolve_weights(args.image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--image_encoder', refusal='the DAMSM image encoder weights are needed')
     cfg_from_file(args.cfg)
     if args.token_ids and cfg.TEXT.ENCODER_NAME != 'RNN':
         raise SystemExit(f'--token_ids feeds the RNN encoder; TEXT.ENCODER_NAME is {cfg.TEXT.ENCODER_NAME} (use --captions)')
@@ -70,12 +69,11 @@ def _check_args(args):
 def main(argv=None):
     args = parse_args(argv)
     files = _check_args(args)
-    import numpy as np
     import torch
     from xmc_gan import sample
     from xmc_gan.config.gan import cfg
     from xmc_gan_amd import rprecision as RP
-    from xmc_gan_amd.fid import _read_rgb
+    from xmc_gan_amd.fid import decoded_batches
     args.synthetic, args.sbert_dir = 0, (args.text_encoder or '') if cfg.TEXT.ENCODER_NAME == 'SBERT' else ''
     tokens, lens, lines = sample._load_captions(args)
     n, K = len(lines), args.per_caption
@@ -99,21 +97,9 @@ def main(argv=None):
         for i in range(0, n, args.batch):
             sents.append(text_encoder(tokens[i:i + args.batch], lens[i:i + args.batch])[1].detach().float())
     rp = RP.RPrecision(args.k, args.splits, args.seed)
-    # decoded as `stats_of_dir` does: PIL on a few host threads, the files of a batch that share a size through the encoder together
-    from concurrent.futures import ThreadPoolExecutor
-    try:
-        cores = len(os.sched_getaffinity(0))
-    except AttributeError:
-        cores = os.cpu_count() or 1
     codes = torch.empty((n * K, image_encoder.nef), dtype=torch.float32, device=device)
-    with ThreadPoolExecutor(max(1, min(8, cores))) as pool:
-        for i in range(0, len(files), args.batch):
-            groups = {}
-            for j, arr in enumerate(pool.map(_read_rgb, files[i:i + args.batch])):
-                groups.setdefault(arr.shape, []).append((i + j, arr))
-            for members in groups.values():
-                idx = torch.tensor([m[0] for m in members], device=device)
-                codes[idx] = image_encoder.encode_u8(torch.from_numpy(np.stack([m[1] for m in members])))[1]
+    for idx, u8 in decoded_batches(files, args.batch):       # (the files of a batch that share a size go through the encoder together)
+        codes[torch.tensor(idx, device=device)] = image_encoder.encode_u8(u8)[1]
     rp.update(codes, torch.cat(sents), torch.arange(n).repeat_interleave(K))
     try:
         result = rp.finalize()

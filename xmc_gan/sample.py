@@ -31,6 +31,7 @@ from xmc_gan.dataset import sent_to_index
 from xmc_gan.train_gan import _DISC_ARCH, _GEN_ARCH, _TEXT_ARCH, SyntheticCOCO, SyntheticTextEncoder
 from xmc_gan.utils.visual import PngPool
 from xmc_gan_amd import ops
+from xmc_gan_amd.evaluate import MetricSuite, image_set_kind, load_model, resolve_weights
 from xmc_gan_amd.infer import Sampler, slerp, truncated_noise
 
 
@@ -103,25 +104,17 @@ def _check_args(args):
         raise SystemExit('--walk / --interp_sent need at least 2 frames')
     if args.walk and max(args.n_per_caption, args.best_of) < 2:
         raise SystemExit("--walk goes from a caption's first noise to its second: ask for --n_per_caption 2 (or more)")
-    if args.fid_against:
-        args.fid_inception = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
-        if not (os.path.isdir(args.fid_against) or (os.path.isfile(args.fid_against) and args.fid_against.endswith('.npz'))):
-            raise SystemExit(f'--fid_against: {args.fid_against} is neither an image directory nor an .npz statistics file')
-        if not args.fid_inception or not os.path.isfile(args.fid_inception):
-            raise SystemExit(f'--fid_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
-    if args.prdc_against:
-        args.fid_inception = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
-        if not (os.path.isdir(args.prdc_against) or (os.path.isfile(args.prdc_against) and args.prdc_against.endswith('.npz'))):
-            raise SystemExit(f'--prdc_against: {args.prdc_against} is neither an image directory nor an .npz feature file')
-        if not 1 <= args.prdc_k <= 16:
-            raise SystemExit(f'--prdc_k: {args.prdc_k}; 1 <= K <= 16 expected')
-        if not args.fid_inception or not os.path.isfile(args.fid_inception):
-            raise SystemExit(f'--prdc_against needs the FID Inception weights: --fid_inception PATH or XMC_FID_INCEPTION (got {args.fid_inception!r})')
+    for flag, path, holds in (('--fid_against', args.fid_against, 'statistics'), ('--prdc_against', args.prdc_against, 'feature')):
+        if path:
+            if image_set_kind(path) is None:
+                raise SystemExit(f'{flag}: {path} is neither an image directory nor an .npz {holds} file')
+            if flag == '--prdc_against' and not 1 <= args.prdc_k <= 16:
+                raise SystemExit(f'--prdc_k: {args.prdc_k}; 1 <= K <= 16 expected')
+            args.fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception',
+                                                 refusal=f'{flag} needs the FID Inception weights')
     if args.rprecision:
-        args.damsm_image_encoder = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
-        if not args.damsm_image_encoder or not os.path.isfile(args.damsm_image_encoder):
-            raise SystemExit(f'--rprecision needs the DAMSM image encoder weights: --damsm_image_encoder PATH or XMC_DAMSM_IMAGE_ENCODER '
-                             f'(got {args.damsm_image_encoder!r})')
+        args.damsm_image_encoder = resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder',
+                                                   refusal='--rprecision needs the DAMSM image encoder weights')
         if args.rp_k < 2 or args.rp_splits < 1:
             raise SystemExit('--rp_k must be >= 2 and --rp_splits >= 1')
     cfg_from_file(args.cfg)
@@ -202,6 +195,13 @@ def _row_grid(x8_frames, path):
     Image.fromarray(ops.image_grid_u8(x8_frames, nrow=x8_frames.size(0)).cpu().numpy()).save(path)
 
 
+_SCORES = {     # metric of MetricSuite.results(): (the flag that asked for it, its printed line, its manifest key)
+    'FID': ('--fid_against', 'FID: {FID}', 'fid'),
+    'PRDC': ('--prdc_against', 'precision: {precision} recall: {recall} density: {density} coverage: {coverage} (k={k}, n={n_real}/{n_fake})', 'prdc'),
+    'R-precision': ('--rprecision', 'R-precision: {r_precision} +- {std} (k={k}, n={n})', 'r_precision'),
+}
+
+
 def main(argv=None):
     args = parse_args(argv)
     _check_args(args)
@@ -250,28 +250,18 @@ def main(argv=None):
     n_grid = min(n * K, args.grid_max)
     kept = torch.empty((n_grid, S, S, 8), dtype=ops.act_dtype(), device=device) if n_grid else None      # the grid's images, engine layout
     images, pool = [], (None if args.no_png else PngPool())
-    fid_ex = fid_stats = None
-    if args.fid_against:                                             # the sampled images are scored from the device, as the bytes of the PNGs
-        from xmc_gan.utils.visual import fid_extractor
-        from xmc_gan_amd.fid import FeatureStats, frechet_distance, stats_of
-        fid_ex, fid_stats = fid_extractor(args.fid_inception, device), FeatureStats(device=device)
-    prdc_bank = None
-    if args.prdc_against:                                            # the same extractor (and the same pass) as --fid_against when both are given
-        from xmc_gan.utils.visual import fid_extractor
-        from xmc_gan_amd import manifold as MF
-        fid_ex = fid_ex or fid_extractor(args.fid_inception, device)
-        prdc_bank = MF.FeatureBank(device=device)
-    rp = rp_enc = None
     if args.rprecision:
-        from xmc_gan_amd import rprecision as RP
         try:
-            rp_enc = RP.load_image_encoder(args.damsm_image_encoder, None, device)
+            load_model('damsm', args.damsm_image_encoder, device)
         except (ImportError, ValueError) as e:
             raise SystemExit(f'--damsm_image_encoder: {e}')
-        why = RP.usable_with(text_encoder, rp_enc)
-        if why:
-            raise SystemExit(f'--rprecision: {why}')
-        rp = RP.RPrecision(args.rp_k, args.rp_splits, args.seed)
+    # the sampled images are scored from the device, as the bytes of the PNGs (xmc_gan_amd/evaluate.py: one pass serves every metric asked for)
+    suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against) else '', args.prdc_k if args.prdc_against else 0,
+                        args.damsm_image_encoder if args.rprecision else '', text_encoder, args.rp_k, args.rp_splits, args.seed,
+                        fid=bool(args.fid_against))
+    for metric, why in suite.why.items():
+        raise SystemExit(f'{_SCORES[metric][0]}: {why}')
+    suite.real_from_path(args.fid_against, args.prdc_against, bs)
     cap_step = max(1, bs // M)                                       # captions per batch: about `bs` forwards' worth of images
     try:
         for c0 in range(0, n, cap_step):
@@ -287,14 +277,7 @@ def main(argv=None):
                 u8, sc = ops.image_to_u8(x8), None
             if c0 * K < n_grid:
                 kept[c0 * K:min(n_grid, c1 * K)] = x8[:n_grid - c0 * K]
-            if fid_ex is not None:
-                feats = fid_ex(u8)
-                if fid_stats is not None:
-                    fid_stats.update(feats)
-                if prdc_bank is not None:
-                    prdc_bank.update(feats)
-            if rp is not None:                                       # image r of the batch was made from caption r // K
-                rp.update(rp_enc.encode_u8(u8)[1], sents[c0:c1], torch.arange(nc).repeat_interleave(K))
+            suite.update_fake(u8, sents[c0:c1], torch.arange(nc).repeat_interleave(K))       # image r of the batch was made from caption r // K
             host = u8.cpu().numpy()                                  # one copy per batch: 3 bytes per pixel
             for r in range(nc * K):
                 c, k = c0 + r // K, r % K
@@ -328,35 +311,18 @@ def main(argv=None):
         from PIL import Image
         grid = 'grid.png'
         Image.fromarray(ops.image_grid_u8(kept).cpu().numpy()).save(os.path.join(args.out, grid))
-    fid = None
-    if fid_stats is not None:
-        if fid_stats.n < 2:
-            raise SystemExit('--fid_against: a covariance needs at least two sampled images')
-        fid = frechet_distance(*stats_of(args.fid_against, fid_ex, bs), *fid_stats.finalize())
-        print(f'FID: {fid}')
-    prdc = None
-    if prdc_bank is not None:
-        try:
-            prdc = MF.prdc(MF.bank_of(args.prdc_against, fid_ex, bs, device), prdc_bank, args.prdc_k)
-        except ValueError as e:
-            raise SystemExit(f'--prdc_against: {e}')
-        print(f'precision: {prdc["precision"]} recall: {prdc["recall"]} density: {prdc["density"]} coverage: {prdc["coverage"]} '
-              f'(k={prdc["k"]}, n={prdc["n_real"]}/{prdc["n_fake"]})')
-    r_precision = None
-    if rp is not None:
-        try:
-            r_precision = rp.finalize()
-        except ValueError as e:
-            raise SystemExit(f'--rprecision: {e}')
-        print(f'R-precision: {r_precision["r_precision"]} +- {r_precision["std"]} (k={r_precision["k"]}, n={r_precision["n"]})')
+    scores = {}
+    for metric, values, why in suite.results():
+        flag, line, key = _SCORES[metric]
+        if values is None:
+            raise SystemExit(f'{flag}: {"a covariance needs at least two sampled images" if metric == "FID" else why}')
+        print(line.format(**values))
+        scores[key] = values
     manifest = dict(checkpoint=os.path.abspath(args.checkpoint), netD=os.path.abspath(args.netD) if args.netD else None,
                     cfg=os.path.abspath(args.cfg), config_name=cfg.CONFIG_NAME, generator=cfg.GEN.ENCODER_NAME, img_size=S,
                     seed=args.seed, precision=ops.precision(), truncation=args.truncation, n_per_caption=K, best_of=args.best_of or None,
-                    captions=n, fid=fid, grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
-    if rp is not None:                                               # (only with --rprecision: the manifest of every other run is unchanged)
-        manifest['r_precision'] = r_precision
-    if prdc is not None:                                             # (only with --prdc_against)
-        manifest['prdc'] = prdc
+                    captions=n, fid=scores.pop('fid', {}).get('FID'), grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
+    manifest.update({key: scores[key] for key in ('r_precision', 'prdc') if key in scores})     # (only when asked for, in the order of before)
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

@@ -22,6 +22,7 @@ if PROJ_DIR not in sys.path:
     sys.path.append(PROJ_DIR)
 
 import argparse
+import collections
 import random
 import time
 
@@ -36,9 +37,10 @@ from xmc_gan.model.concept_gan import InNetG as CONCEPT_INATTN_GEN, OutNetG as C
 from xmc_gan.model.encoder import RNN_ENCODER, SBERT_ENCODER
 from xmc_gan.utils.logger import setup_logger
 from xmc_gan.utils.miscc import count_params
-from xmc_gan.utils.visual import ScalarLog, fid_between, fid_extractor, flush_saves, save_image, save_image_async, to_uint8_hwc
+from xmc_gan.utils.visual import ScalarLog, fid_between, flush_saves, save_image, save_image_async, to_uint8_hwc
 from xmc_gan_amd import ops, parallel
 from xmc_gan_amd.augment import DiffAugment, parse_policy
+from xmc_gan_amd.evaluate import MetricSuite, resolve_weights
 from xmc_gan_amd.optim import HipAdam, ParamEMA
 
 _GEN_ARCH = {"DF_GEN": DF_GEN, "CONCEPT_IN_DF_GEN": CONCEPT_IN_DF_GEN, "CONCEPT_OUT_DF_GEN": CONCEPT_OUT_DF_GEN,
@@ -514,7 +516,7 @@ class _DeviceBatches:
 
 
 def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, optimizerG, optimizerD, logger, model_dir,
-          opts=None, img_dir=None, max_steps=None, writer=None):
+          opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None):
     """Epoch loop with the reference's signature (train_gan.py:142); returns the last iteration's losses.
 
     With ``img_dir`` (rank 0) it keeps the reference's visual log: ``sents.txt`` and ``imgs.png`` of the first batch (146-160),
@@ -530,7 +532,8 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
     written into a second, eval-mode generator that exists for nothing else (the captured iteration never sees it); checkpoints
     add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training.
 
-    ``opts.diffaug`` (a `DiffAugment`, ``--diffaug``): its rows are redrawn before every iteration, graphed or eager."""
+    ``opts.diffaug`` (a `DiffAugment`, ``--diffaug``): its rows are redrawn before every iteration, graphed or eager.
+    ``eval_opts`` (an `EvalOptions`): what `eval` scores after an epoch, handed on to it."""
     device = next(netG.parameters()).device
     opts = opts or StepOptions()
     ema = opts.ema
@@ -646,7 +649,8 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
                 eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder,
                      netG=netG_ema if ema is not None else netG,
                      logger=logger, num_samples=6000,
-                     save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None, writer=writer)
+                     save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None, writer=writer,
+                     eval_opts=eval_opts)
     flush_saves()                    # the sample grids queued for the writer thread are on disk when train() returns
     last = _detached(last)
     if thr is not None:
@@ -662,71 +666,29 @@ def _detached(last):
     return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in last.items()}
 
 
-_FID_INCEPTION = ['']        # --fid_inception (main()); eval() falls back to $XMC_FID_INCEPTION
+# what `eval` scores after an epoch (not part of the reference cfg; main() fills one from --fid_inception, --prdc and --damsm_image_encoder)
+EvalOptions = collections.namedtuple('EvalOptions', 'fid_inception prdc_k damsm_image_encoder', defaults=('', 0, ''))
 
 
-_PRDC_K = [0]                # --prdc (main())
-_DAMSM_IMAGE_ENCODER = ['']  # --damsm_image_encoder (main()); eval() falls back to $XMC_DAMSM_IMAGE_ENCODER
-_damsm_cache = {}
-
-
-def _damsm_encoder(path, device):
-    """the DAMSM image encoder of a weights file, loaded once per (file, device)"""
-    key = (os.path.abspath(path), os.stat(path).st_mtime_ns if os.path.isfile(path) else None, str(device))
-    if key not in _damsm_cache:
-        from xmc_gan_amd.rprecision import load_image_encoder
-        _damsm_cache.clear()
-        _damsm_cache[key] = load_image_encoder(path, None, device)
-    return _damsm_cache[key]
-
-
-def _fid_u8(images_nchw, device):
-    """[B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] on the device: trunc((x + 1) * 127.5), the bytes eval() writes into the PNGs"""
-    from xmc_gan_amd.fid import nchw_to_u8
-    return nchw_to_u8(images_nchw.to(device))
-
-
-def _real_bank(loader, extractor, device, limit):
-    """feature rows of the loader's real images alone (the cached ones were made for another number of samples)"""
-    from xmc_gan_amd.manifold import FeatureBank
-    bank = FeatureBank(device=device)
-    for imgs, _, _ in loader:
-        bank.update(extractor(_fid_u8(imgs, device)))
-        if bank.n >= limit:
-            break
-    return bank
-
-
-def _real_stats(loader, extractor, device, limit):
-    """statistics of the loader's real images alone (the cached ones were made for another number of samples)"""
-    from xmc_gan_amd.fid import FeatureStats
-    st = FeatureStats(device=device)
-    for imgs, _, _ in loader:
-        st.update(extractor(_fid_u8(imgs, device)))
-        if st.n >= limit:
-            break
-    return st
+_EVAL_REPORT = {    # metric of MetricSuite.results(): (its log line, the values that are scalars of that name, the line that says why there is none)
+    'FID': (' epoch {epoch}, FID : {FID}', ('FID',), ' epoch {epoch}, generated {cnt} images (FID not computed: {why})'),
+    'PRDC': (' epoch {epoch}, precision : {precision} recall : {recall} density : {density} coverage : {coverage} (k={k}, n={n_real}/{n_fake})',
+             ('precision', 'recall', 'density', 'coverage'), ' epoch {epoch}, precision / recall / density / coverage not computed: {why}'),
+    'R-precision': (' epoch {epoch}, R-precision : {r_precision} +- {std} (k={k}, n={n})', ('r_precision',),
+                    ' epoch {epoch}, R-precision not computed: {why}'),
+}
 
 
 @torch.no_grad()
 def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
-         damsm_image_encoder=None, metrics=None, prdc=None):
-    """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to
-    ``save_dir/<key>.png`` and, unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``,
-    as 8-bit PNGs of (x + 1) * 127.5.  FID (logged and written to the scalar log as 'FID'):
-    with ``fid_inception`` (default: --fid_inception, then $XMC_FID_INCEPTION) on this project's kernels -- the generated images go to the
-    extractor from the device as the bytes the PNGs hold, the real images' statistics are computed once and cached beside ``org_dir`` as
-    ``org_stats.npz`` (reused while its sample count matches); otherwise between the two directories when ``pytorch_fid`` is importable.
-    R-precision (logged, written as 'R_precision', and put into ``metrics`` when a dict is passed): with ``damsm_image_encoder`` (default:
-    --damsm_image_encoder, then $XMC_DAMSM_IMAGE_ENCODER), the DAMSM image encoder's weights -- the same bytes go through
-    ``CNN_ENCODER.encode_u8`` and are paired with the loop's ``sent_embs`` (k = 100 candidates, 10 splits; xmc_gan_amd/rprecision.py).  Only
-    with an ``RNN_ENCODER`` of the image encoder's width; otherwise one line says why it was not computed.
-    Precision / recall / density / coverage (logged, written as 'precision', 'recall', 'density', 'coverage', and put into ``metrics`` with
-    'prdc_k', 'n_real', 'n_fake'): with ``prdc`` = K > 0 (default: --prdc) and the FID extractor -- the feature batches FID takes also go into two
-    ``FeatureBank``s (xmc_gan_amd/manifold.py); the real rows are cached beside ``org_stats.npz`` as ``org_features.npz`` (reused while the
-    row count matches).  Without the Inception weights one line says why nothing was computed.  FID's value and line are what they are
-    without it.
-    Returns (uint8 tensor of the generated images, FID or None)."""
+         damsm_image_encoder=None, metrics=None, prdc=None, eval_opts=None):
+    """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to ``save_dir/<key>.png`` and,
+    unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``, as 8-bit PNGs of (x + 1) * 127.5.  The
+    scores are a `MetricSuite`'s (xmc_gan_amd/evaluate.py): FID with ``fid_inception`` (without it: between the two directories, when
+    ``pytorch_fid`` imports), precision / recall / density / coverage with ``prdc`` = K > 0 beside it, R-precision with ``damsm_image_encoder``
+    and an ``RNN_ENCODER``; each is the keyword, else ``eval_opts``, else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER.  With ``org_dir`` the real
+    side is cached beside it.  Every score is logged (or one line says why there is none), written to ``writer`` and, FID apart, put into
+    ``metrics`` when a dict is passed ('k' of PRDC as 'prdc_k').  Returns (uint8 tensor of the generated images, FID or None)."""
     from PIL import Image
     netG.eval()
     device = next(netG.parameters()).device
@@ -736,40 +698,12 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     if org_dir:
         os.makedirs(org_dir, exist_ok=True)
         save_org = len(os.listdir(org_dir)) != num_samples
-    weights = fid_inception or _FID_INCEPTION[0] or os.environ.get('XMC_FID_INCEPTION', '')
-    extractor = gen_stats = real_stats = cached = cache = None
-    if weights:
-        from xmc_gan_amd.fid import FeatureStats, frechet_distance, load_stats
-        extractor = fid_extractor(weights, device)
-        gen_stats = FeatureStats(device=device)
-        cache = os.path.join(os.path.dirname(os.path.abspath(org_dir)), 'org_stats.npz') if org_dir else None
-        if cache and os.path.isfile(cache):
-            cached = load_stats(cache, with_count=True)
-        if cached is None:
-            real_stats = FeatureStats(device=device)
-    prdc_k = int(_PRDC_K[0] if prdc is None else prdc)
-    gen_bank = real_bank = bank_cache = prdc_why = None
-    if prdc_k > 0 and extractor is None:
-        prdc_why = 'it takes the Inception features of FID: --fid_inception PATH or XMC_FID_INCEPTION'
-    elif prdc_k > 0:
-        from xmc_gan_amd import manifold as MF
-        gen_bank = MF.FeatureBank(device=device)
-        bank_cache = os.path.join(os.path.dirname(os.path.abspath(org_dir)), 'org_features.npz') if org_dir else None
-        cached_bank = None
-        if bank_cache and os.path.isfile(bank_cache):
-            try:
-                cached_bank = MF.FeatureBank.load(bank_cache, device)
-            except ValueError:
-                cached_bank = None
-        real_bank = MF.FeatureBank(device=device) if cached_bank is None else None
-    damsm = damsm_image_encoder or _DAMSM_IMAGE_ENCODER[0] or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
-    image_encoder = rprec = rprec_why = None
-    if damsm:
-        from xmc_gan_amd import rprecision as RP
-        image_encoder = _damsm_encoder(damsm, device)
-        rprec_why = RP.usable_with(text_encoder, image_encoder)
-        if rprec_why is None:
-            rprec = RP.RPrecision()
+    given = eval_opts or EvalOptions()
+    suite = MetricSuite(device, fid_inception or given.fid_inception or os.environ.get('XMC_FID_INCEPTION', ''),
+                        given.prdc_k if prdc is None else prdc,
+                        damsm_image_encoder or given.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', ''), text_encoder)
+    if org_dir:
+        suite.open_cache(os.path.dirname(os.path.abspath(org_dir)))
     cnt, outs = 0, []
     for imgs, texts_lst, keys in loader:
         caps, cap_lens = texts_lst[0]
@@ -777,20 +711,8 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
-        fake_u8 = _fid_u8(fake, device) if (extractor is not None or rprec is not None) else None
-        if rprec is not None:
-            rprec.update(image_encoder.encode_u8(fake_u8)[1], sent_embs)
-        if extractor is not None:
-            feats = extractor(fake_u8)
-            gen_stats.update(feats)
-            if gen_bank is not None:
-                gen_bank.update(feats)
-            if real_stats is not None or real_bank is not None:
-                feats = extractor(_fid_u8(imgs, device))
-                if real_stats is not None:
-                    real_stats.update(feats)
-                if real_bank is not None:
-                    real_bank.update(feats)
+        suite.update_fake(fake, sent_embs)
+        suite.update_real(imgs)              # (taken only while a metric lacks its real side)
         for j in range(fake.size(0)):
             if save_dir:
                 Image.fromarray(to_uint8_hwc(fake[j])).save(f'{save_dir}/{keys[j]}.png')
@@ -799,61 +721,25 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         cnt += fake.size(0)
         if cnt >= num_samples:
             break
-    if extractor is not None:
-        fid, why = None, 'fewer than two images'
-        if cnt >= 2:
-            if cached is not None and cached[2] == cnt:
-                real = cached[:2]
-            else:
-                if real_stats is None:        # a cache for another number of samples
-                    real_stats = _real_stats(loader, extractor, device, cnt)
-                real = real_stats.finalize()
-                if cache:
-                    real_stats.save(cache)
-            fid = frechet_distance(*real, *gen_stats.finalize())
-    else:
-        fid, why = (fid_between(org_dir, save_dir, device) if (save_dir and org_dir and cnt) else None), 'pytorch_fid is not installed'
-    if fid is None:
-        logger.info(f' epoch {state_epoch}, generated {cnt} images (FID not computed: {why})')
-    else:
-        logger.info(f' epoch {state_epoch}, FID : {fid}')
-        if writer is not None:
-            writer.add_scalar('FID', fid, state_epoch)
-    if gen_bank is not None:
-        if real_bank is None and cached_bank.n == cnt:
-            real_bank = cached_bank
-        else:
-            if real_bank is None:             # a cache for another number of samples
-                real_bank = _real_bank(loader, extractor, device, cnt)
-            if bank_cache and real_bank.n:
-                real_bank.save(bank_cache)
-        try:
-            r = MF.prdc(real_bank, gen_bank, prdc_k)
-        except ValueError as e:
-            r, prdc_why = None, str(e)
-        if r is not None:
-            logger.info(f' epoch {state_epoch}, precision : {r["precision"]} recall : {r["recall"]} density : {r["density"]} '
-                        f'coverage : {r["coverage"]} (k={r["k"]}, n={r["n_real"]}/{r["n_fake"]})')
-            for name in ('precision', 'recall', 'density', 'coverage'):
-                if writer is not None:
-                    writer.add_scalar(name, r[name], state_epoch)
-            if metrics is not None:
-                metrics.update({name: r[name] for name in ('precision', 'recall', 'density', 'coverage', 'n_real', 'n_fake')}, prdc_k=r['k'])
-    if prdc_why is not None:
-        logger.info(f' epoch {state_epoch}, precision / recall / density / coverage not computed: {prdc_why}')
-    if rprec is not None:
-        try:
-            r = rprec.finalize()
-        except ValueError as e:
-            r, rprec_why = None, str(e)
-        if r is not None:
-            logger.info(f' epoch {state_epoch}, R-precision : {r["r_precision"]} +- {r["std"]} (k={r["k"]}, n={r["n"]})')
+    suite.real_from_cache(cnt, lambda: (imgs for imgs, _, _ in loader))
+    results = list(suite.results())
+    if not results or results[0][0] != 'FID':     # no Inception weights: between the two directories, where pytorch_fid imports
+        fid = fid_between(org_dir, save_dir, device) if (save_dir and org_dir and cnt) else None
+        results.insert(0, ('FID', None if fid is None else dict(FID=fid), 'pytorch_fid is not installed'))
+    fid = None
+    for metric, values, why in results:
+        line, tags, line_without = _EVAL_REPORT[metric]
+        if values is None:
+            logger.info(line_without.format(epoch=state_epoch, cnt=cnt, why=why))
+            continue
+        logger.info(line.format(epoch=state_epoch, **values))
+        for key in tags:
             if writer is not None:
-                writer.add_scalar('R_precision', r['r_precision'], state_epoch)
-            if metrics is not None:
-                metrics.update(r)
-    if rprec_why is not None:
-        logger.info(f' epoch {state_epoch}, R-precision not computed: {rprec_why}')
+                writer.add_scalar('R_precision' if key == 'r_precision' else key, values[key], state_epoch)
+        if metric == 'FID':
+            fid = values['FID']
+        elif metrics is not None:
+            metrics.update({('prdc_k' if (metric, k) == ('PRDC', 'k') else k): v for k, v in values.items()})
     return (torch.cat(outs) if outs else None), fid
 
 
@@ -891,15 +777,11 @@ def main(argv=None):
         cfg.TRAIN.MAX_EPOCH = args.max_epoch
     if args.precision:
         ops.set_precision(args.precision)
-    _FID_INCEPTION[0] = args.fid_inception or os.environ.get('XMC_FID_INCEPTION', '')
-    if _FID_INCEPTION[0] and not os.path.isfile(_FID_INCEPTION[0]):
-        raise SystemExit(f'--fid_inception: {_FID_INCEPTION[0]} is not a file')
+    fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception', must_exist=False)
     if not 0 <= args.prdc <= 16:
         raise SystemExit('--prdc K: 0 (off) or 1 <= K <= 16 nearest neighbours')
-    _PRDC_K[0] = args.prdc
-    _DAMSM_IMAGE_ENCODER[0] = args.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', '')
-    if _DAMSM_IMAGE_ENCODER[0] and not os.path.isfile(_DAMSM_IMAGE_ENCODER[0]):
-        raise SystemExit(f'--damsm_image_encoder: {_DAMSM_IMAGE_ENCODER[0]} is not a file')
+    eval_opts = EvalOptions(fid_inception, args.prdc,
+                            resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False))
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', str(args.gpu_id)))
@@ -1045,7 +927,7 @@ def main(argv=None):
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
                  opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
                                   ema=ema, diffaug=aug),
-                 img_dir=img_dir if rank == 0 else None, writer=writer)
+                 img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts)
     if writer is not None:
         writer.close()
     torch.cuda.synchronize()

@@ -217,17 +217,10 @@ class ScalarLog:
             self._f.close()
 
 
-_fid_extractors = {}
-
-
 def fid_extractor(weights, device):
-    """the native Inception feature extractor of ``weights`` on ``device`` (xmc_gan_amd.fid.InceptionFID), built once per file and device"""
-    import torch
-    from xmc_gan_amd.fid import InceptionFID
-    key = (os.path.abspath(weights), str(torch.device(device)))
-    if key not in _fid_extractors:
-        _fid_extractors[key] = InceptionFID(weights, device)
-    return _fid_extractors[key]
+    """the native Inception feature extractor of ``weights`` on ``device`` (xmc_gan_amd.fid.InceptionFID via xmc_gan_amd.evaluate.load_model)"""
+    from xmc_gan_amd.evaluate import load_model
+    return load_model('inception', weights, device)
 
 
 def fid_between(dir_a, dir_b, device, batch_size=100, dims=2048, weights=None):
