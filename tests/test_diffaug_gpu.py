@@ -269,13 +269,27 @@ def test_gradient_through_the_discriminator_fp32():
     assert (got[..., C:] == 0).all()
 
 
-def test_identity_rows_through_the_iteration_fp32():
-    """all-identity rows: the D step's forward-only losses are bit-equal to the iteration without the option, the losses behind an optimizer
-    step within the fp32 loss bar of tests/test_models_gpu.py (1e-3 relative, 1e-4 absolute).  With MA-GP, ENCODER_LOSS.SENT and RMIS_LOSS."""
+@pytest.mark.parametrize("route,over,at_the_bar", [
+    ("one 2B pass", {}, ()),                                                # real and generated images in one engine-layout buffer
+    ("three passes", {"DISC.SPEC_NORM": True}, ("errD_real", "errD_fake", "errD_mismatch", "ds_loss")),      # both in the engine layout, MA-GP under ops.composable()
+    ("generated image as NCHW", {"GEN.ENCODER_NAME": "CONCEPT_OUTATTN_GEN"}, ("errD_fake", "fake")),      # a generator without nhwc_out
+], ids=["one-2B-pass", "three-passes", "generated-image-as-NCHW"])
+def test_identity_rows_through_the_iteration_fp32(route, over, at_the_bar):
+    """all-identity rows: the D step's forward-only losses and the generated image are bit-equal to the iteration without the option, the
+    losses behind an optimizer step within the fp32 loss bar of tests/test_models_gpu.py (1e-3 relative, 1e-4 absolute).  With MA-GP,
+    ENCODER_LOSS.SENT, ENCODER_LOSS.DISC (the generator step's second pass over the real images) and RMIS_LOSS, on each of the three ways an
+    image reaches the discriminator.
+
+    ``at_the_bar``: what is not bit-equal on a route, compared at that loss bar instead (per element for the image).  Measured in four runs
+    each before and after the iteration was split into phases, with the same figures: under spectral norm any two discriminators built
+    from the same weights differ by an ulp or two in their logits, so the three hinge terms differ by 0 .. 2.4e-7 from run to run (ds_loss by 0
+    in all eight runs, the image by 0: the generator is not involved); the word-attention generator's image differs by 1.4e-6 .. 2.4e-6
+    between any two runs (f32 atomics order of its BatchNorm sums) and errD_fake with it by 2.4e-7 .. 9.5e-7, the quantities that depend on
+    the real images alone by 0."""
     import xmc_gan.train_gan as tg
     ops.set_precision("fp32")
-    cfg, h = setup_cfg("df_gan_damsm.yml", **{"TRAIN.NCH": 8})
-    assert cfg.TRAIN.MAGP and cfg.TRAIN.RMIS_LOSS and cfg.TRAIN.ENCODER_LOSS.SENT
+    cfg, h = setup_cfg("df_gan_damsm.yml", **{"TRAIN.NCH": 8, **over})
+    assert cfg.TRAIN.MAGP and cfg.TRAIN.RMIS_LOSS and cfg.TRAIN.ENCODER_LOSS.SENT and cfg.TRAIN.ENCODER_LOSS.DISC
     b = X.synth_batch(h, 4, seed=500, words_len=cfg.TEXT.MAX_LENGTH)
     batch = [b[k].to(DEV) for k in ("imgs", "sent_embs", "words_embs", "mask", "noise")]
     outs = []
@@ -287,11 +301,15 @@ def test_identity_rows_through_the_iteration_fp32():
         outs.append({k: v.float().cpu() for k, v in o.items()})
     plain, ident = outs
     assert set(plain) == set(ident)
-    exact = ("errD_real", "errD_fake", "errD_mismatch", "ds_loss")
-    for k in exact:
-        assert torch.equal(plain[k], ident[k]), (k, plain[k], ident[k])
-    assert torch.equal(plain["fake"], ident["fake"])
-    for k in sorted(set(plain) - set(exact) - {"fake"}):
+    forward_only = ("errD_real", "errD_fake", "errD_mismatch", "ds_loss", "fake")
+    print(f"\n  [identity rows, {route}] forward-only differences: " + ", ".join(f"{k} {float((plain[k] - ident[k]).abs().max()):.3g}"
+                                                                                for k in forward_only))
+    for k in forward_only:
+        if k in at_the_bar:
+            assert ((ident[k] - plain[k]).abs() <= 1e-3 * plain[k].abs() + 1e-4).all(), (k, plain[k], ident[k])
+        else:
+            assert torch.equal(plain[k], ident[k]), (k, plain[k], ident[k])
+    for k in sorted(set(plain) - set(forward_only)):
         a, r = float(ident[k]), float(plain[k])
         print(f"  [identity rows] {k}: {a:.7g} vs {r:.7g}")
         assert abs(a - r) <= 1e-3 * (6.0 if k == "d_loss_gp" else 1.0) * abs(r) + 1e-4, (k, a, r)

@@ -21,6 +21,11 @@ from . import ops
 _active = None          # the GraphedIteration whose capture is running (collectives consult it through seam())
 
 
+class CaptureFailed(RuntimeError):
+    """a capture that did not come about (an operator that synchronises, memory): nothing it recorded ever ran, so its caller may run the
+    batch with eager launches instead.  Warm-up iterations and replays raise what they raise."""
+
+
 def _quiesce():
     """Called outside capture, before a capture is opened or re-opened: nothing of a collective may be pending anywhere.  The `nccl` process
     group's watchdog thread polls the end event of every collective it has not yet seen complete (every 100 ms); on this ROCm such a poll
@@ -174,7 +179,10 @@ class GraphedIteration:
             return self.step_fn(*self.static_in, self.it_state)
         phase = self._phase()
         if phase not in self.seqs:
-            self._capture(phase)
+            try:
+                self._capture(phase)
+            except Exception as e:
+                raise CaptureFailed(f"{type(e).__name__}: {e}") from e
         for item in self.seqs[phase]:
             item()
         # the replay changed the weights without the host-side bookkeeping of an eager optimizer step: packed copies made since

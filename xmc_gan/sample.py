@@ -28,7 +28,7 @@ import torch
 
 from xmc_gan.config.gan import cfg, cfg_from_file
 from xmc_gan.dataset import sent_to_index
-from xmc_gan.train_gan import _DISC_ARCH, _GEN_ARCH, _TEXT_ARCH, SyntheticCOCO, SyntheticTextEncoder
+from xmc_gan.train_gan import _DISC_ARCH, _GEN_ARCH, SyntheticCOCO, build_text_encoder
 from xmc_gan.utils.visual import PngPool
 from xmc_gan_amd import ops
 from xmc_gan_amd.evaluate import MetricSuite, image_set_kind, load_model, resolve_weights
@@ -174,19 +174,11 @@ def _load_captions(args):
 
 
 def _text_encoder(args, device):
-    if args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':       # as train_gan.main() picks them
-        return SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, args.seed, device)
-    if cfg.TEXT.ENCODER_NAME == 'SBERT':      # frozen weights from its model directory: no state dict to load (the reference has none either)
-        return _TEXT_ARCH['SBERT'](cfg=cfg, model_dir=args.sbert_dir or None).to(device).eval()
-    enc = _TEXT_ARCH[cfg.TEXT.ENCODER_NAME](cfg=cfg).to(device)      # (random weights come from torch.manual_seed(--seed) in main())
-    path = args.text_encoder if args.text_encoder is not None else (f'{PROJ_DIR}/{cfg.TEXT.ENCODER_DIR}' if cfg.TEXT.ENCODER_DIR else '')
-    if path and (args.text_encoder is not None or args.synthetic <= 0 or os.path.isfile(path)):
-        enc.load_state_dict(torch.load(path, map_location=device))
-    elif args.synthetic <= 0:
+    """the trainer's encoder for this cfg (random weights come from torch.manual_seed(--seed) in main()), or --text_encoder's state dict"""
+    enc, has_weights = build_text_encoder(device, args.seed, args.synthetic > 0, args.sbert_dir, weights=args.text_encoder)
+    if not has_weights and args.synthetic <= 0:
         print('sample.py: no text encoder weights (--text_encoder / TEXT.ENCODER_DIR): the encoder is randomly initialised', file=sys.stderr)
-    for p_ in enc.parameters():
-        p_.requires_grad = False
-    return enc.eval()
+    return enc
 
 
 def _row_grid(x8_frames, path):

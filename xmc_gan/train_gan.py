@@ -25,6 +25,7 @@ import argparse
 import collections
 import random
 import time
+import types
 
 import numpy as np
 import torch
@@ -41,6 +42,7 @@ from xmc_gan.utils.visual import ScalarLog, fid_between, flush_saves, save_image
 from xmc_gan_amd import ops, parallel
 from xmc_gan_amd.augment import DiffAugment, parse_policy
 from xmc_gan_amd.evaluate import MetricSuite, resolve_weights
+from xmc_gan_amd.graph import CaptureFailed, GraphedIteration
 from xmc_gan_amd.optim import HipAdam, ParamEMA
 
 _GEN_ARCH = {"DF_GEN": DF_GEN, "CONCEPT_IN_DF_GEN": CONCEPT_IN_DF_GEN, "CONCEPT_OUT_DF_GEN": CONCEPT_OUT_DF_GEN,
@@ -185,23 +187,23 @@ def _set_requires_grad(module, flag):
 
 def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_embs, mask, noise, it_state,
                   opts=None):
-    """One pass of the reference loop body (train_gan.py:185-291) on device tensors.
+    """One pass of the reference loop body (train_gan.py:185-291) on device tensors: the generated image, then `_d_step`, `_gp_step` and
+    `_g_step`, which share an `_Iteration`.
 
     Returns a dict of 0-d loss tensors (no host sync).  ``it_state['i']`` carries the N_CRITIC counter.
     """
     opts = opts or StepOptions()
-    T, E = cfg.TRAIN, cfg.TRAIN.ENCODER_LOSS
     batch_size = mask.size(0)
     ops.new_iteration(imgs.device)                 # one memset for all weight-gradient scratch of this iteration
-    gather = parallel.gather_rows if opts.gather_negatives else (lambda t: t)
-    gather_all = parallel.gather_rows_multi if opts.gather_negatives else (lambda ts: list(ts))     # several tensors, one collective
-    out = {}
-
-    # ---- discriminator step (train_gan.py:187-229)
+    see = _DInput(netD, opts.diffaug, batch_size)
     psent_embs = sent_embs if cfg.DISC.SEPERATE else netG.proj_sent(sent_embs.float())
     nhwc_g = bool(getattr(netG, 'nhwc_out', False))             # generator can hand out its image in the engine layout
+    # The discriminator does not couple the samples of a batch, so its passes over the real and the generated images
+    # (193, 202) run as ONE pass over 2B images and the three COND_DNET calls (194, 203, 208) as one over 3B-1 rows: same
+    # values, half the launches, twice the work per launch on the small maps at the end of D.  Not with spectral norm: there
+    # every forward CALL advances the power iteration (modules.py:16-17), so the call pattern is part of the result.
     batched = nhwc_g and isinstance(netD, DF_DISC) and not cfg.DISC.SPEC_NORM and ops.fused_blocks() and not ops.debug_switch('no_d2b')
-    # the discriminator's 2B-image input of the batched pass below: the real images are converted into its first half, the
+    # the discriminator's 2B-image input of the batched pass: the real images are converted into its first half, the
     # generator's last convolution writes its second half (no concatenation pass)
     both_h = (torch.empty((2 * batch_size, imgs.shape[2], imgs.shape[3], 8), dtype=ops.act_dtype(), device=imgs.device)
               if batched and getattr(netG, 'nhwc_dst_ok', False) else None)
@@ -212,188 +214,174 @@ def gan_iteration(netG, netD, optimizerG, optimizerD, imgs, sent_embs, words_emb
     else:
         fake, fake_h = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask), None
     # converted once, used by both steps
-    imgs_h = ops.to_nhwc8(imgs, out=both_h[:batch_size] if both_h is not None else None) if isinstance(netD, DF_DISC) else None
-    # The discriminator does not couple the samples of a batch, so its passes over the real and the generated images
-    # (193, 202) run as ONE pass over 2B images and the three COND_DNET calls (194, 203, 208) as one over 3B-1 rows: same
-    # values, half the launches, twice the work per launch on the small maps at the end of D.  Not with spectral norm: there
-    # every forward CALL advances the power iteration (modules.py:16-17), so the call pattern is part of the result.
-    # data parallel: the trunk is handed out where it enters D's last blocks, for the two-part backward below (parallel.py)
+    imgs_h = ops.to_nhwc8(imgs, out=both_h[:batch_size] if both_h is not None else None) if see.engine else None
+    # data parallel: the trunk is handed out where it enters D's last blocks, for the two-part backward of the D step (parallel.py)
     cuts = [] if (parallel.active() and isinstance(netD, DF_DISC) and netD.cut_block() is not None
                   and not ops.debug_switch('no_dp_overlap')) else None
-    netD.cut_sink = cuts
-    # differentiable augmentation (opts.diffaug; not in the reference): EVERY image netD sees below goes through ops.diffaug first, with the
-    # rows of the sampler's static device tensor that belong to the pass.  `out['fake']`, the sample grids and eval() keep the plain images.
-    aug = opts.diffaug
-    if aug is not None and aug.batch != batch_size:
-        raise ValueError(f'DiffAugment was built for batches of {aug.batch}, got {batch_size}')
+    it = _Iteration(netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, opts=opts, see=see, batch_size=batch_size,
+                    imgs=imgs, imgs_h=imgs_h, fake=fake, fake_h=fake_h, both_h=both_h, batched=batched, cuts=cuts,
+                    sent_embs=sent_embs, psent_embs=psent_embs, labels=None, out={},
+                    gather=parallel.gather_rows if opts.gather_negatives else (lambda t: t),
+                    gather_all=parallel.gather_rows_multi if opts.gather_negatives else (lambda ts: list(ts)))   # several tensors, one collective
+    _d_step(it)
+    if cfg.TRAIN.MAGP:
+        _gp_step(it)
+    it_state['i'] = it_state.get('i', 0) + 1
+    if it_state['i'] % cfg.TRAIN.N_CRITIC == 0:
+        _g_step(it)
+        it_state['i'] = 0
+    it.out['fake'] = fake.detach()
+    ops.end_iteration(imgs.device)                 # forward-only code between iterations (evaluation, sampling) stays out of the arena
+    return it.out
 
-    def augmented_features(x, x_h, rows):
-        """netD's features of the augmented images: x NCHW, x_h the same in the engine layout (or None)"""
-        if isinstance(netD, DF_DISC):
-            return netD(None, nhwc8=aug(x_h if x_h is not None else ops.to_nhwc8(x), rows))
-        return netD(ops.to_nchw(aug(ops.to_nhwc8(x), rows), x.shape[1]))       # a discriminator without an engine-layout entrance
-    if imgs_h is not None and fake_h is not None and not cfg.DISC.SPEC_NORM and ops.fused_blocks() and not ops.debug_switch('no_d2b'):
-        B = batch_size
-        x2b = both_h if both_h is not None else torch.cat((imgs_h, fake_h.detach()))
-        feats = netD(None, nhwc8=x2b if aug is None else aug(x2b, aug.rows_d()))
-        real_features, fake_features = feats[:B], feats[B:]
-        ps_d = psent_embs.detach()
+
+class _DInput:
+    """How ``netD`` sees an image; built once per iteration.  The one place that knows the engine layout's entrance (``nhwc8=``), the
+    conversions and the augmentation (opts.diffaug; not in the reference): with it EVERY image netD sees goes through ops.diffaug first,
+    with the rows of the sampler's static device tensor that belong to the pass, while `out['fake']`, the sample grids and eval() keep the
+    plain images."""
+
+    def __init__(self, netD, aug, batch_size):
+        if aug is not None and aug.batch != batch_size:
+            raise ValueError(f'DiffAugment was built for batches of {aug.batch}, got {batch_size}')
+        self.netD, self.aug = netD, aug
+        self.engine = isinstance(netD, DF_DISC)         # (a discriminator of another class has no engine-layout entrance)
+
+    def rows(self, which):
+        """the augmentation rows of the pass 'd' (2B), 'real', 'fake' or 'g'; None without augmentation"""
+        return None if self.aug is None else getattr(self.aug, 'rows_' + which)()
+
+    def __call__(self, x, x_h, rows):
+        """netD's features of the images ``x`` (NCHW; may be None when ``x_h`` is given), ``x_h`` the same in the engine layout [B,H,W,8] or
+        None, augmented with ``rows`` unless None.  What NetD.forward infers from its arguments stays with it (df_gan.py:145-150)."""
+        netD = self.netD
+        if not self.engine:
+            return netD(x) if rows is None else netD(ops.to_nchw(self.aug(ops.to_nhwc8(x), rows), x.shape[1]))
+        if rows is None:
+            return netD(x, nhwc8=x_h) if x_h is not None else netD(x)
+        return netD(None, nhwc8=self.aug(x_h if x_h is not None else ops.to_nhwc8(x), rows))
+
+
+class _Iteration(types.SimpleNamespace):
+    """What the phases of one iteration share: the modules, optimizers and ``opts``; the batch (``imgs``, ``imgs_h`` its engine layout or
+    None, ``sent_embs``, ``psent_embs``) and the generated images (``fake``, ``fake_h``); ``see`` (the `_DInput`), ``batched`` with its input
+    buffer ``both_h``, ``cuts``, the gather functions; ``labels``, which the D step leaves for the G step; ``out``, the returned losses."""
+
+
+def _scaled(loss, scaler):
+    """IEEE-half mode only (ops.set_precision): each backward runs on a dynamic, device-resident scale x its loss (keeps 1/B-sized
+    gradients normal), HipAdam reads the f32 parameter gradients times 1 / scale and SKIPS the step on the device when one
+    of them is inf / NaN (after the all-reduce, so every rank decides alike).  ``scaler`` is None in the other modes."""
+    return scaler.scale(loss) if scaler is not None else loss
+
+
+def _backward_in_two_parts(loss, netD, cuts):
+    """D's head and last three blocks hold 93 % of its gradient bytes (75 of 81 MB at 256 px) and their backward is the first quarter of
+    the pass (small maps); the blocks before the cut hold 7 % and take the rest of the time (large maps).  The first part's all-reduce is
+    started as soon as its gradients exist and runs beside the second part; same gradients as one `.backward()` (autograd executes the
+    same nodes in the same order, in two calls)."""
+    late, early = netD.late_parameters()
+    late = [p_ for p_ in late if p_.requires_grad]
+    gs = torch.autograd.grad(loss, cuts + late, allow_unused=True)
+    for p_, g_ in zip(late, gs[len(cuts):]):
+        p_.grad = g_
+    pending = parallel.allreduce_mean_grads_begin(late)
+    reached = [(c_, g_) for c_, g_ in zip(cuts, gs) if g_ is not None]          # (a handed-out tensor the loss does not use has no gradient)
+    torch.autograd.backward([c_ for c_, _ in reached], [g_ for _, g_ in reached])
+    parallel.allreduce_mean_grads_end(pending, early)
+
+
+def _d_step(it):
+    """the discriminator step (train_gan.py:187-229)"""
+    T, E, netD, see, B, out = cfg.TRAIN, cfg.TRAIN.ENCODER_LOSS, it.netD, it.see, it.batch_size, it.out
+    ps_d = it.psent_embs.detach()
+    fake_hd = it.fake_h.detach() if it.fake_h is not None else None
+    netD.cut_sink = it.cuts
+    # the two forms differ in how they come by (outputs_real, logits_real, logits_fake, logits_mismatch or None)
+    if it.batched:      # one pass over 2B images, one COND_DNET call over 3B-1 rows
+        x2b = it.both_h if it.both_h is not None else torch.cat((it.imgs_h, fake_hd))
+        feats = see(None, x2b, see.rows('d'))
+        real_features = feats[:B]
         rows = [feats, real_features[:B - 1]] if T.RMIS_LOSS else [feats]
         sents = [ps_d, ps_d, ps_d[1:B]] if T.RMIS_LOSS else [ps_d, ps_d]
         o_all = netD.COND_DNET(torch.cat(rows) if T.RMIS_LOSS else feats, sent_embs=torch.cat(sents))
         outputs_real = [o[:B] for o in o_all]
-        errD_real = ops.hinge(o_all[0][:B], -1.0)
-        errD_fake = ops.hinge(o_all[0][B:2 * B], 1.0)
-        mis_loss = errD_fake
-        if T.RMIS_LOSS:
-            errD_mismatch = ops.hinge(o_all[0][2 * B:], 1.0)
-            mis_loss = mis_loss + errD_mismatch
-            out['errD_mismatch'] = errD_mismatch.detach()
-    else:
-        if aug is not None:
-            real_features = augmented_features(imgs, imgs_h, aug.rows_real())
-        else:
-            real_features = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
-        outputs_real = netD.COND_DNET(real_features, sent_embs=psent_embs.detach())
-        errD_real = ops.hinge(outputs_real[0], -1.0)
-        if aug is not None:
-            fake_features = augmented_features(fake.detach(), fake_h.detach() if fake_h is not None and imgs_h is not None else None,
-                                               aug.rows_fake())
-        else:
-            fake_features = netD(fake.detach(), nhwc8=fake_h.detach()) if fake_h is not None and imgs_h is not None else netD(fake.detach())
-        outputs_fake = netD.COND_DNET(fake_features, sent_embs=psent_embs.detach())
-        errD_fake = ops.hinge(outputs_fake[0], 1.0)
-        mis_loss = errD_fake
-        if T.RMIS_LOSS:
-            outputs_mis = netD.COND_DNET(real_features[:(batch_size - 1)], sent_embs=psent_embs[1:batch_size].detach())
-            errD_mismatch = ops.hinge(outputs_mis[0], 1.0)
-            mis_loss = mis_loss + errD_mismatch
-            out['errD_mismatch'] = errD_mismatch.detach()
+        logits_real, logits_fake = o_all[0][:B], o_all[0][B:2 * B]
+        logits_mismatch = o_all[0][2 * B:] if T.RMIS_LOSS else None
+    else:               # the reference's calls, one by one (193-194, 202-203, 208)
+        real_features = see(it.imgs, it.imgs_h, see.rows('real'))
+        outputs_real = netD.COND_DNET(real_features, sent_embs=ps_d)
+        fake_features = see(it.fake.detach(), fake_hd, see.rows('fake'))
+        logits_real, logits_fake = outputs_real[0], netD.COND_DNET(fake_features, sent_embs=ps_d)[0]
+        logits_mismatch = netD.COND_DNET(real_features[:B - 1], sent_embs=it.psent_embs[1:B].detach())[0] if T.RMIS_LOSS else None
     netD.cut_sink = None
-    labels = None
-    n_rows = batch_size * (parallel.world() if opts.gather_negatives else 1)
+    errD_real = ops.hinge(logits_real, -1.0)
+    errD_fake = ops.hinge(logits_fake, 1.0)
+    mis_loss = errD_fake
+    if T.RMIS_LOSS:
+        errD_mismatch = ops.hinge(logits_mismatch, 1.0)
+        mis_loss = mis_loss + errD_mismatch
+        out['errD_mismatch'] = errD_mismatch.detach()
+    n_rows = B * (parallel.world() if it.opts.gather_negatives else 1)
     enc_loss = 0.
     if E.SENT:
         assert cfg.DISC.SENT_MATCH or cfg.DISC.IMG_MATCH
         # (the sentence embeddings the labels are made from travel with the two embeddings the loss compares: one collective)
-        g_sent, g_img, g_txt = gather_all((sent_embs.float(), outputs_real[1], outputs_real[2]))
-        labels = make_labels(n_rows, sent_embs=g_sent, b_global=E.B_GLOBAL)
-        ds_loss = sent_loss(imgs=g_img, txts=g_txt, labels=labels, b_global=E.B_GLOBAL)
+        g_sent, g_img, g_txt = it.gather_all((it.sent_embs.float(), outputs_real[1], outputs_real[2]))
+        it.labels = make_labels(n_rows, sent_embs=g_sent, b_global=E.B_GLOBAL)
+        ds_loss = sent_loss(imgs=g_img, txts=g_txt, labels=it.labels, b_global=E.B_GLOBAL)
         enc_loss = enc_loss + T.SMOOTH.SENT * ds_loss
         out['ds_loss'] = ds_loss.detach()
     elif E.WORD or E.DISC or E.VGG:
-        labels = make_labels(n_rows, sent_embs=gather(sent_embs.float()), b_global=E.B_GLOBAL)
+        it.labels = make_labels(n_rows, sent_embs=it.gather(it.sent_embs.float()), b_global=E.B_GLOBAL)
     if E.WORD:
         raise NotImplementedError
     errD = errD_real + (mis_loss * T.SMOOTH.MISMATCH) + enc_loss
-    netG.zero_grad()
+    it.netG.zero_grad()
     netD.zero_grad()
-    # IEEE-half mode only (ops.set_precision): each backward runs on a dynamic, device-resident scale x its loss (keeps 1/B-sized
-    # gradients normal), HipAdam reads the f32 parameter gradients times 1 / scale and SKIPS the step on the device when one
-    # of them is inf / NaN (after the all-reduce, so every rank decides alike).  None in the other modes.
-    sc_d = ops.loss_scaler("D", imgs.device)
-    loss_d = sc_d.scale(errD) if sc_d is not None else errD
-    if cuts:
-        # Backward in two parts.  D's head and last three blocks hold 93 % of its gradient bytes (75 of 81 MB at 256 px) and their backward
-        # is the first quarter of the pass (small maps); the blocks before the cut hold 7 % and take the rest of the time (large maps).  The
-        # first part's all-reduce is started as soon as its gradients exist and runs beside the second part; same gradients as one
-        # `.backward()` (autograd executes the same nodes in the same order, in two calls).
-        late, early = netD.late_parameters()
-        late = [p_ for p_ in late if p_.requires_grad]
-        gs = torch.autograd.grad(loss_d, cuts + late, allow_unused=True)
-        for p_, g_ in zip(late, gs[len(cuts):]):
-            p_.grad = g_
-        pending = parallel.allreduce_mean_grads_begin(late)
-        reached = [(c_, g_) for c_, g_ in zip(cuts, gs) if g_ is not None]          # (a handed-out tensor the loss does not use has no gradient)
-        torch.autograd.backward([c_ for c_, _ in reached], [g_ for _, g_ in reached])
-        parallel.allreduce_mean_grads_end(pending, early)
+    sc_d = ops.loss_scaler("D", it.imgs.device)
+    if it.cuts:
+        _backward_in_two_parts(_scaled(errD, sc_d), netD, it.cuts)
     else:
-        loss_d.backward()
+        _scaled(errD, sc_d).backward()
         parallel.allreduce_mean_grads(netD.parameters())
-    _step(optimizerD, sc_d)
+    _step(it.optimizerD, sc_d)
     out.update(errD=errD.detach(), errD_real=errD_real.detach(), errD_fake=errD_fake.detach())
 
-    # ---- matching-aware gradient penalty on real pairs (train_gan.py:231-252)
-    if T.MAGP:
-        interpolated = imgs.detach().requires_grad_()
-        sent_inter = psent_embs.detach().requires_grad_()
-        # this forward's backward is differentiated again.  The fused discriminator blocks carry their own second-order node
-        # (ops.ResDBwdFn); with spectral norm the blocks are composed from the fine-grained Functions as before
-        # ops.second_order(): the blocks keep their residual branch (not just its sign bits) for the linearised forward
-        with (ops.composable() if cfg.DISC.SPEC_NORM else contextlib.nullcontext()), ops.second_order():
-            # (augmented: the penalty is taken where the discriminator is evaluated, and differentiated through the augmentation)
-            features = netD(interpolated) if aug is None else augmented_features(interpolated, None, aug.rows_real())
-            o = netD.COND_DNET(features, sent_inter)
-        s_in = ops.gp_inner_scale()    # IEEE-half mode: the inner backward runs on s_in x ones, the penalty divides it out
-        with ops.no_wgrad():           # first-order pass only needs d(logit)/d(inputs)
-            grads = torch.autograd.grad(outputs=o[0], inputs=(interpolated, sent_inter),
-                                        grad_outputs=torch.full_like(o[0], s_in), retain_graph=True, create_graph=True,
-                                        only_inputs=True)
-        # mean(||cat(grad0, grad1)||_2 ** 6) (241-247) in two passes over the 3*S*S-wide image gradient, no concatenation
-        d_loss_gp = ops.grad_penalty(grads[0], grads[1], inner_scale=s_in)
-        d_loss = 2.0 * d_loss_gp
-        optimizerD.zero_grad()
-        optimizerG.zero_grad()
-        sc_gp = ops.loss_scaler("GP", imgs.device)
-        (sc_gp.scale(d_loss) if sc_gp is not None else d_loss).backward()
-        # the reference's autograd hands zero (not None) grads to every bias that feeds the logit
-        # (their only path is through LeakyReLU'' == 0), which still advances Adam's moments/step.
-        for name, p_ in netD.named_parameters():
-            if p_.grad is None and name.endswith('.bias') and 'proj_match' not in name and _bias_on_logit_path(netD, name):
-                p_.grad = torch.zeros_like(p_)
-        parallel.allreduce_mean_grads(netD.parameters())
-        _step(optimizerD, sc_gp)
-        out['d_loss_gp'] = d_loss_gp.detach()
 
-    # ---- generator step (train_gan.py:254-291)
-    it_state['i'] = it_state.get('i', 0) + 1
-    if it_state['i'] % T.N_CRITIC == 0:
-        _set_requires_grad(netD, False)          # D's weight grads would be discarded (zero_grad at 226-227)
-        try:
-            if aug is not None:
-                features = augmented_features(fake, fake_h if fake_h is not None and imgs_h is not None else None, aug.rows_g())
-            else:
-                features = netD(fake, nhwc8=fake_h) if fake_h is not None and imgs_h is not None else netD(fake)
-            outputs = netD.COND_DNET(features, sent_embs=psent_embs)
-            errG_fake = -outputs[0].float().mean()
-            enc_loss = 0.0
-            real_pooled = fake_pooled = None
-            if E.DISC:
-                with torch.no_grad():
-                    if aug is not None:                  # the same rows as the generated images it is compared with
-                        real_again = augmented_features(imgs, imgs_h, aug.rows_g())
-                    else:
-                        real_again = netD(imgs, nhwc8=imgs_h) if imgs_h is not None else netD(imgs)
-                    real_pooled = ops.global_avgpool(real_again.permute(0, 2, 3, 1).contiguous())
-                fake_pooled = ops.global_avgpool(features.permute(0, 2, 3, 1).contiguous())
-            # what the contrastive terms of this step compare across ranks, all-gathered in ONE collective (a seam of the captured iteration each)
-            rows = gather_all(([outputs[1], outputs[2]] if E.SENT else []) + ([real_pooled, fake_pooled] if E.DISC else []))
-            if E.SENT:
-                gs_loss = sent_loss(imgs=rows[0], txts=rows[1], labels=labels, b_global=E.B_GLOBAL)
-                enc_loss = enc_loss + T.SMOOTH.SENT * gs_loss
-                out['gs_loss'] = gs_loss.detach()
-            if E.WORD:
-                raise NotImplementedError
-            if E.DISC:
-                disc_loss = img_loss(real_imgs=rows[-2], fake_imgs=rows[-1], labels=labels, b_global=E.B_GLOBAL)
-                enc_loss = enc_loss + T.SMOOTH.DISC * disc_loss
-                out['disc_loss'] = disc_loss.detach()
-            if E.VGG:
-                raise NotImplementedError
-            errG = errG_fake + enc_loss
-            netG.zero_grad()
-            netD.zero_grad()
-            sc_g = ops.loss_scaler("G", imgs.device)
-            (sc_g.scale(errG) if sc_g is not None else errG).backward()
-        finally:
-            _set_requires_grad(netD, True)
-        parallel.allreduce_mean_grads(netG.parameters())
-        _step(optimizerG, sc_g, opts.ema)
-        it_state['i'] = 0
-        out.update(errG=errG.detach(), errG_fake=errG_fake.detach())
-    out['fake'] = fake.detach()
-    ops.end_iteration(imgs.device)                 # forward-only code between iterations (evaluation, sampling) stays out of the arena
-    return out
+def _gp_step(it):
+    """the matching-aware gradient penalty on real pairs (train_gan.py:231-252)"""
+    netD, see = it.netD, it.see
+    interpolated = it.imgs.detach().requires_grad_()
+    sent_inter = it.psent_embs.detach().requires_grad_()
+    # this forward's backward is differentiated again.  The fused discriminator blocks carry their own second-order node
+    # (ops.ResDBwdFn); with spectral norm the blocks are composed from the fine-grained Functions as before
+    # ops.second_order(): the blocks keep their residual branch (not just its sign bits) for the linearised forward
+    with (ops.composable() if cfg.DISC.SPEC_NORM else contextlib.nullcontext()), ops.second_order():
+        # (the leaf itself goes in as x.  Augmented: the penalty is taken where the discriminator is evaluated, and differentiated
+        # through the augmentation)
+        features = see(interpolated, None, see.rows('real'))
+        o = netD.COND_DNET(features, sent_inter)
+    s_in = ops.gp_inner_scale()    # IEEE-half mode: the inner backward runs on s_in x ones, the penalty divides it out
+    with ops.no_wgrad():           # first-order pass only needs d(logit)/d(inputs)
+        grads = torch.autograd.grad(outputs=o[0], inputs=(interpolated, sent_inter),
+                                    grad_outputs=torch.full_like(o[0], s_in), retain_graph=True, create_graph=True,
+                                    only_inputs=True)
+    # mean(||cat(grad0, grad1)||_2 ** 6) (241-247) in two passes over the 3*S*S-wide image gradient, no concatenation
+    d_loss_gp = ops.grad_penalty(grads[0], grads[1], inner_scale=s_in)
+    d_loss = 2.0 * d_loss_gp
+    it.optimizerD.zero_grad()
+    it.optimizerG.zero_grad()
+    sc_gp = ops.loss_scaler("GP", it.imgs.device)
+    _scaled(d_loss, sc_gp).backward()
+    # the reference's autograd hands zero (not None) grads to every bias that feeds the logit
+    # (their only path is through LeakyReLU'' == 0), which still advances Adam's moments/step.
+    for name, p_ in netD.named_parameters():
+        if p_.grad is None and name.endswith('.bias') and 'proj_match' not in name and _bias_on_logit_path(netD, name):
+            p_.grad = torch.zeros_like(p_)
+    parallel.allreduce_mean_grads(netD.parameters())
+    _step(it.optimizerD, sc_gp)
+    it.out['d_loss_gp'] = d_loss_gp.detach()
 
 
 def _bias_on_logit_path(netD, name):
@@ -403,6 +391,46 @@ def _bias_on_logit_path(netD, name):
     if name.startswith('downblocks.') and name.endswith('.conv_s.bias'):
         return netD.downblocks[int(name.split('.')[1])].learned_shortcut
     return False
+
+
+def _g_step(it):
+    """the generator step (train_gan.py:254-291)"""
+    T, E, netD, see, out = cfg.TRAIN, cfg.TRAIN.ENCODER_LOSS, it.netD, it.see, it.out
+    _set_requires_grad(netD, False)          # D's weight grads would be discarded (zero_grad at 226-227)
+    try:
+        features = see(it.fake, it.fake_h, see.rows('g'))
+        outputs = netD.COND_DNET(features, sent_embs=it.psent_embs)
+        errG_fake = -outputs[0].float().mean()
+        enc_loss = 0.0
+        real_pooled = fake_pooled = None
+        if E.DISC:
+            with torch.no_grad():            # (augmented: the same rows as the generated images it is compared with)
+                real_pooled = ops.global_avgpool(see(it.imgs, it.imgs_h, see.rows('g')).permute(0, 2, 3, 1).contiguous())
+            fake_pooled = ops.global_avgpool(features.permute(0, 2, 3, 1).contiguous())
+        # what the contrastive terms of this step compare across ranks, all-gathered in ONE collective (a seam of the captured iteration each)
+        rows = it.gather_all(([outputs[1], outputs[2]] if E.SENT else []) + ([real_pooled, fake_pooled] if E.DISC else []))
+        if E.SENT:
+            gs_loss = sent_loss(imgs=rows[0], txts=rows[1], labels=it.labels, b_global=E.B_GLOBAL)
+            enc_loss = enc_loss + T.SMOOTH.SENT * gs_loss
+            out['gs_loss'] = gs_loss.detach()
+        if E.WORD:
+            raise NotImplementedError
+        if E.DISC:
+            disc_loss = img_loss(real_imgs=rows[-2], fake_imgs=rows[-1], labels=it.labels, b_global=E.B_GLOBAL)
+            enc_loss = enc_loss + T.SMOOTH.DISC * disc_loss
+            out['disc_loss'] = disc_loss.detach()
+        if E.VGG:
+            raise NotImplementedError
+        errG = errG_fake + enc_loss
+        it.netG.zero_grad()
+        netD.zero_grad()
+        sc_g = ops.loss_scaler("G", it.imgs.device)
+        _scaled(errG, sc_g).backward()
+    finally:
+        _set_requires_grad(netD, True)
+    parallel.allreduce_mean_grads(it.netG.parameters())
+    _step(it.optimizerG, sc_g, it.opts.ema)
+    out.update(errG=errG.detach(), errG_fake=errG_fake.detach())
 
 
 # --------------------------------------------------------------------------------------- synthetic front end
@@ -515,6 +543,166 @@ class _DeviceBatches:
                 nxt = None
 
 
+def encode(text_encoder, caps, cap_lens, keys):
+    """(words_embs, sent_embs, mask) of a batch: a CachedTextEncoder looks it up by its keys, an encoder encodes the captions"""
+    return text_encoder.forward_keys(keys) if hasattr(text_encoder, 'forward_keys') else text_encoder(caps, cap_lens)
+
+
+def _log_first_batch(img_dir, train_loader, caps, cap_lens, imgs_host, sent_embs, words_embs, mask, device):
+    """``sents.txt`` and ``imgs.png`` of the first batch (train_gan.py:146-160); returns the fixed noise and captions of the per-epoch grids"""
+    i2w = getattr(getattr(train_loader, 'dataset', None), 'i2w', None)
+    with open(f'{img_dir}/sents.txt', 'w') as f:
+        if torch.is_tensor(caps):            # WORD captions: token ids (index_to_sent, dataset.py) or the ids themselves
+            for row, n in zip(caps.tolist(), torch.as_tensor(cap_lens).tolist()):
+                f.write((' '.join(i2w[t] for t in row[:n]) if i2w else ' '.join(str(t) for t in row[:n])) + ' \n')
+        else:                                # SENT captions: the sentences
+            for sent in caps:
+                f.write(f'{sent} \n')
+    fixed = dict(noise=torch.randn(mask.size(0), cfg.TRAIN.NOISE_DIM).to(device), sent=sent_embs.clone(),
+                 words=words_embs.clone(), mask=mask.clone())
+    save_image(imgs_host, f'{img_dir}/imgs.png', normalize=True, scale_each=True)
+    return fixed
+
+
+def _graphed_iteration(step_fn, inputs):
+    return GraphedIteration(step_fn, inputs, n_critic=cfg.TRAIN.N_CRITIC, warmup=2)
+
+
+class IterationRunner:
+    """Runs a batch as hipGraph replays (``use_graph``; the graphed object is made from the first batch by ``factory``) or with eager
+    launches: ``--graph 0``, a batch of another shape than the captured one (a loader without drop_last), and every batch after a capture
+    that failed in a single process.  Nothing else is caught: a warm-up iteration or a replay that raises may already have applied an
+    optimizer step, so running that batch again would step twice.  Owns the N_CRITIC counter ``it_state``."""
+
+    def __init__(self, step_fn, logger, use_graph, factory=_graphed_iteration):
+        self.step_fn, self.logger, self.use_graph, self.factory = step_fn, logger, use_graph, factory
+        self.it_state, self.graphed = {}, None
+
+    @property
+    def hipgraph(self):
+        return self.graphed is not None
+
+    def __call__(self, inputs):
+        if self.use_graph and self.graphed is None:
+            self.graphed = self.factory(self.step_fn, inputs)
+            self.graphed.it_state = self.it_state
+        if self.graphed is not None and all(s_.shape == t_.shape and s_.dtype == t_.dtype for s_, t_ in zip(self.graphed.static_in, inputs)):
+            try:
+                return dict(self.graphed(*inputs))
+            except CaptureFailed as e:       # (an operator that synchronises, memory): nothing the capture recorded has run
+                if parallel.world() > 1:
+                    raise                    # the ranks' collectives are out of step: no in-band way to agree on a fallback
+                self.logger.info(f'hipGraph capture failed ({e}); continuing with eager launches')
+                self.it_state = dict(self.graphed.it_state)
+                self.close()
+                self.use_graph = False
+        return self.step_fn(*inputs, self.it_state)
+
+    def close(self):
+        if self.graphed is not None:
+            self.graphed.close()
+            self.graphed = None
+
+
+class _Throughput:
+    """The run's images/s: from the end of step _TIMED_FROM (warm-ups and captures done) to the end of each epoch, one synchronisation
+    per epoch.  ``last`` is the latest report, the ``throughput`` entry of what train() returns."""
+
+    def __init__(self, device, logger):
+        self.device, self.logger, self.t0, self.n0, self.last = device, logger, None, 0, None
+
+    def after_step(self, nsteps):
+        if self.device.type == 'cuda' and self.t0 is None and nsteps == _TIMED_FROM + 2 * (cfg.TRAIN.N_CRITIC - 1):
+            torch.cuda.synchronize(self.device)
+            self.t0, self.n0 = time.perf_counter(), nsteps + 1
+
+    def after_epoch(self, nsteps, hipgraph):
+        if self.t0 is None or nsteps <= self.n0:
+            return
+        torch.cuda.synchronize(self.device)
+        dt_, n_ = time.perf_counter() - self.t0, nsteps - self.n0
+        thr = self.last = dict(steps=n_, seconds=round(dt_, 4), ms_per_step=round(1e3 * dt_ / n_, 3),
+                               images_per_s=round(parallel.world() * cfg.TRAIN.BATCH_SIZE * n_ / dt_, 1), hipgraph=hipgraph)
+        self.logger.info(f'throughput: {thr["images_per_s"]} images/s ({thr["ms_per_step"]} ms per iteration over {n_} iterations, '
+                         f'{"hipGraph replay" if hipgraph else "eager launches"})')
+        self.t0, self.n0 = time.perf_counter(), nsteps
+
+
+_CHECKPOINT = dict(netG='netG_{:03d}.pth', netD='netD_{:03d}.pth', optimizerG='optimizerG.pth', optimizerD='optimizerD.pth',
+                   loss_scale='loss_scale.pth', netG_ema='netG_ema_{:03d}.pth', ema_state='ema_state.pth')
+
+
+def _ckpt(model_dir, what, epoch):
+    return f'{model_dir}/{_CHECKPOINT[what].format(epoch)}'
+
+
+def save_checkpoint(model_dir, epoch, netG, netD, optimizerG, optimizerD, ema=None, netG_ema=None):
+    """The reference's four files (train_gan.py:328-334); ``loss_scale.pth`` where there is scaler state (IEEE-half mode: the dynamic loss
+    scales are optimizer state too); with ``ema``, the averaged generator ``netG_ema`` as a plain generator state dict, loadable wherever
+    ``netG_<epoch>.pth`` is, and the average's counter."""
+    for what, obj in (('netG', netG), ('netD', netD), ('optimizerG', optimizerG), ('optimizerD', optimizerD)):
+        torch.save(obj.state_dict(), _ckpt(model_dir, what, epoch))
+    if ops.loss_scaler_state():
+        torch.save(ops.loss_scaler_state(), _ckpt(model_dir, 'loss_scale', epoch))
+    if ema is not None:
+        torch.save(netG_ema.state_dict(), _ckpt(model_dir, 'netG_ema', epoch))
+        torch.save(dict(num_updates=int(ema.num_updates.item()), decay=ema.decay, start=ema.start), _ckpt(model_dir, 'ema_state', epoch))
+
+
+def load_checkpoint(model_dir, epoch, netG, netD, optimizerG, optimizerD, ema=None, *, device, logger):
+    """`save_checkpoint`'s files of ``epoch`` back into the objects; ``ema`` (a `ParamEMA` of the loaded ``netG``): `load_average` too"""
+    for what, obj in (('netG', netG), ('netD', netD), ('optimizerG', optimizerG), ('optimizerD', optimizerD)):
+        obj.load_state_dict(torch.load(_ckpt(model_dir, what, epoch), map_location=device))
+    if os.path.isfile(_ckpt(model_dir, 'loss_scale', epoch)):
+        ops.load_loss_scaler_state(torch.load(_ckpt(model_dir, 'loss_scale', epoch), map_location='cpu'), device)
+    logger.info(f'Load models, epoch : {epoch}')
+    if ema is not None:
+        load_average(model_dir, epoch, ema, device, logger)
+
+
+def load_average(model_dir, epoch, ema, device, logger):
+    """the average's two files into ``ema``, which was built from the resumed generator: without them (a checkpoint written without the
+    average) it stays a copy of those weights"""
+    f_w, f_s = _ckpt(model_dir, 'netG_ema', epoch), _ckpt(model_dir, 'ema_state', epoch)
+    if not (os.path.isfile(f_w) and os.path.isfile(f_s)):
+        return logger.info(f'no {os.path.basename(f_w)} / {os.path.basename(f_s)} in {model_dir}: the EMA starts from '
+                           f'{os.path.basename(_ckpt(model_dir, "netG", epoch))}')
+    saved = torch.load(f_s, map_location='cpu')
+    ema.load_state_dict(dict(shadow=torch.load(f_w, map_location=device), num_updates=saved['num_updates']))
+    logger.info(f'Load EMA generator, epoch : {epoch} ({saved["num_updates"]} updates; saved with decay {saved["decay"]}, start {saved["start"]})')
+
+
+def _end_of_epoch(epoch, last, *, netG, netD, optimizerG, optimizerD, ema, netG_ema, fixed, img_dir, model_dir, test_loader, text_encoder,
+                  logger, writer, eval_opts):
+    """what the reference does after an epoch's last batch (train_gan.py:300-336): scalars, the sample grid from the fixed batch, and past
+    epoch 50 the checkpoint and `eval`; with ``ema`` the grid, the checkpoint and `eval` take the averaged generator"""
+    if parallel.rank() == 0:
+        _log_epoch_scalars(writer, last, epoch)
+    # IEEE-half mode: the dynamic loss scales and the optimizer steps the found-inf check skipped so far (one host read per epoch)
+    sc_stats = ops.loss_scaler_stats()
+    if sc_stats:
+        last['loss_scale'] = sc_stats
+        logger.info('loss scale ' + ' '.join(f"{k}: {v['scale']:g} ({v['skipped_steps']} skipped)" for k, v in sc_stats.items()))
+        if all(v['scale'] <= 1.0 and v['last_step_skipped'] for v in sc_stats.values()):
+            raise FloatingPointError('every backward of the f16 mode overflows at loss scale 1: the run has diverged')
+    if ema is not None and parallel.rank() == 0:
+        ema.copy_to(netG_ema)                # this epoch's averaged generator (grid, checkpoint, eval)
+    gen = netG_ema if ema is not None else netG
+    if fixed is not None:
+        with torch.no_grad():
+            gen.eval()
+            fake = gen(noise=fixed['noise'], sent_embs=fixed['sent'], words_embs=fixed['words'], mask=fixed['mask'])
+            save_image_async(fake, f'{img_dir}/fake_samples_epoch_{epoch:03d}.png', normalize=True, scale_each=True)
+    if epoch > 50 and parallel.rank() == 0:
+        save_checkpoint(model_dir, epoch, netG, netD, optimizerG, optimizerD, ema, netG_ema)
+        logger.info('Save models')
+        if test_loader is not None:
+            # (--caption_cache: the test split's rows are another table; the train split's encoder carries the test split's)
+            eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder, netG=gen,
+                 logger=logger, num_samples=6000, save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None,
+                 writer=writer, eval_opts=eval_opts)
+
+
 def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, optimizerG, optimizerD, logger, model_dir,
           opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None):
     """Epoch loop with the reference's signature (train_gan.py:142); returns the last iteration's losses.
@@ -538,15 +726,22 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
     opts = opts or StepOptions()
     ema = opts.ema
     netG_ema = type(netG)(cfg).to(device).eval().requires_grad_(False) if ema is not None else None
-    it_state, last, nsteps = {}, {}, 0
-    fixed = None
+    last, nsteps, fixed = {}, 0, None
     visual = img_dir is not None and parallel.rank() == 0
-    graphed, use_graph = None, bool(opts.graph) and device.type == 'cuda'
     batches = _DeviceBatches(train_loader, device)
-    t_mark, thr = [None, 0], None
+    clock = _Throughput(device, logger)
+    runner = IterationRunner(lambda *inputs_and_state: gan_iteration(netG, netD, optimizerG, optimizerD, *inputs_and_state, opts),
+                             logger, use_graph=bool(opts.graph) and device.type == 'cuda')
 
-    def step_fn(imgs_, sent_, words_, mask_, noise_, st_):
-        return gan_iteration(netG, netD, optimizerG, optimizerD, imgs_, sent_, words_, mask_, noise_, st_, opts)
+    def finish():            # the one way out: the sample grids queued for the writer thread are on disk when train() returns
+        flush_saves()
+        out = _detached(last)
+        if clock.last is not None:
+            out['throughput'] = clock.last
+        if runner.hipgraph:
+            out['hipgraph'] = True
+        runner.close()
+        return out
 
     for epoch in range(state_epoch + 1, cfg.TRAIN.MAX_EPOCH + 1):
         netG.train()
@@ -554,50 +749,19 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
         sampler = getattr(train_loader, 'sampler', None)
         if isinstance(sampler, torch.utils.data.distributed.DistributedSampler):
             sampler.set_epoch(epoch)             # data parallel: a new permutation (and new per-rank shards) every epoch
-        for step, data in enumerate(batches):
-            imgs, texts_lst, keys, imgs_host = data
+        for step, (imgs, texts_lst, keys, imgs_host) in enumerate(batches):
             caps, cap_lens = texts_lst[0]
-            with torch.no_grad():       # (a CachedTextEncoder looks the batch up by its keys; an encoder encodes the captions)
-                words_embs, sent_embs, mask = text_encoder.forward_keys(keys) if hasattr(text_encoder, 'forward_keys') else text_encoder(caps, cap_lens)
+            with torch.no_grad():
+                words_embs, sent_embs, mask = encode(text_encoder, caps, cap_lens, keys)
             words_embs, sent_embs = words_embs.detach(), sent_embs.detach()
             if visual and fixed is None:         # the reference takes these from the loader's first batch before the loop
-                i2w = getattr(getattr(train_loader, 'dataset', None), 'i2w', None)
-                with open(f'{img_dir}/sents.txt', 'w') as f:
-                    if torch.is_tensor(caps):            # WORD captions: token ids (index_to_sent, dataset.py) or the ids themselves
-                        for row, n in zip(caps.tolist(), torch.as_tensor(cap_lens).tolist()):
-                            f.write((' '.join(i2w[t] for t in row[:n]) if i2w else ' '.join(str(t) for t in row[:n])) + ' \n')
-                    else:                                # SENT captions: the sentences
-                        for sent in caps:
-                            f.write(f'{sent} \n')
-                fixed = dict(noise=torch.randn(mask.size(0), cfg.TRAIN.NOISE_DIM).to(device), sent=sent_embs.clone(),
-                             words=words_embs.clone(), mask=mask.clone())
-                save_image(imgs_host, f'{img_dir}/imgs.png', normalize=True, scale_each=True)
+                fixed = _log_first_batch(img_dir, train_loader, caps, cap_lens, imgs_host, sent_embs, words_embs, mask, device)
             noise = torch.randn(mask.size(0), cfg.TRAIN.NOISE_DIM).to(device, non_blocking=True)   # CPU generator, as upstream (197-198)
-            inputs = (imgs, sent_embs, words_embs, mask, noise)
             if opts.diffaug is not None:         # new augmentation rows, outside any capture: the replayed kernels read them from the device
                 opts.diffaug.refresh()
-            if use_graph and graphed is None:
-                from xmc_gan_amd.graph import GraphedIteration
-                graphed = GraphedIteration(step_fn, inputs, n_critic=cfg.TRAIN.N_CRITIC, warmup=2)
-                graphed.it_state = it_state
-            if graphed is not None and all(s_.shape == t_.shape and s_.dtype == t_.dtype for s_, t_ in zip(graphed.static_in, inputs)):
-                try:
-                    last = dict(graphed(*inputs))
-                except Exception as e:           # noqa: BLE001 -- a capture that failed (an operator that synchronises, memory)
-                    if parallel.world() > 1:
-                        raise                    # the ranks' collectives are out of step: no in-band way to agree on a fallback
-                    logger.info(f'hipGraph capture failed ({type(e).__name__}: {e}); continuing with eager launches')
-                    it_state = dict(graphed.it_state)
-                    graphed.close()
-                    graphed, use_graph = None, False
-                    last = step_fn(*inputs, it_state)
-            else:                                # eager: --graph 0, or a batch of another shape (a loader without drop_last)
-                last = step_fn(*inputs, it_state)
-            first = nsteps == 0
-            if device.type == 'cuda' and t_mark[0] is None and nsteps == _TIMED_FROM + 2 * (cfg.TRAIN.N_CRITIC - 1):
-                torch.cuda.synchronize(device)           # the run's throughput: from the end of step _TIMED_FROM (warm-ups and captures done) ...
-                t_mark[0], t_mark[1] = time.perf_counter(), nsteps + 1
-            if 'errG' in last and (opts.log_each_step or first or (step + 1) % cfg.TRAIN.LOG_INTERVAL == 0):
+            last = runner((imgs, sent_embs, words_embs, mask, noise))
+            clock.after_step(nsteps)
+            if 'errG' in last and (opts.log_each_step or nsteps == 0 or (step + 1) % cfg.TRAIN.LOG_INTERVAL == 0):
                 logger.info(f'[{epoch}/{cfg.TRAIN.MAX_EPOCH}][{step + 1}/{len(train_loader)}] '
                             f'Loss_D: {last["errD"].item():.3f} Loss_G: {last["errG"].item():.3f} '
                             f'errD_real: {last["errD_real"].item():.3f} errD_fake: {last["errD_fake"].item():.3f} ')
@@ -606,59 +770,12 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
                 save_image_async(last['fake'], f'{img_dir}/fake_samples_{step + 1:03d}.png', normalize=True, scale_each=True)
             nsteps += 1
             if max_steps is not None and nsteps >= max_steps:
-                flush_saves()
-                return _detached(last)
-        if t_mark[0] is not None and nsteps > t_mark[1]:
-            torch.cuda.synchronize(device)               # ... to the end of the epoch (one synchronisation per epoch)
-            dt_, n_ = time.perf_counter() - t_mark[0], nsteps - t_mark[1]
-            thr = dict(steps=n_, seconds=round(dt_, 4), ms_per_step=round(1e3 * dt_ / n_, 3),
-                       images_per_s=round(parallel.world() * cfg.TRAIN.BATCH_SIZE * n_ / dt_, 1), hipgraph=graphed is not None)
-            logger.info(f'throughput: {thr["images_per_s"]} images/s ({thr["ms_per_step"]} ms per iteration over {n_} iterations, '
-                        f'{"hipGraph replay" if graphed is not None else "eager launches"})')
-            t_mark[0], t_mark[1] = time.perf_counter(), nsteps
-        if parallel.rank() == 0:
-            _log_epoch_scalars(writer, last, epoch)
-        # IEEE-half mode: the dynamic loss scales and the optimizer steps the found-inf check skipped so far (one host read per epoch)
-        sc_stats = ops.loss_scaler_stats()
-        if sc_stats:
-            last['loss_scale'] = sc_stats
-            logger.info('loss scale ' + ' '.join(f"{k}: {v['scale']:g} ({v['skipped_steps']} skipped)" for k, v in sc_stats.items()))
-            if all(v['scale'] <= 1.0 and v['last_step_skipped'] for v in sc_stats.values()):
-                raise FloatingPointError('every backward of the f16 mode overflows at loss scale 1: the run has diverged')
-        if ema is not None and parallel.rank() == 0:
-            ema.copy_to(netG_ema)                # this epoch's averaged generator (grid, checkpoint, eval)
-        if visual and fixed is not None:
-            with torch.no_grad():
-                gen = netG_ema if ema is not None else netG
-                gen.eval()
-                fake = gen(noise=fixed['noise'], sent_embs=fixed['sent'], words_embs=fixed['words'], mask=fixed['mask'])
-                save_image_async(fake, f'{img_dir}/fake_samples_epoch_{epoch:03d}.png', normalize=True, scale_each=True)
-        if epoch > 50 and parallel.rank() == 0:
-            torch.save(netG.state_dict(), f'{model_dir}/netG_{epoch:03d}.pth')
-            torch.save(netD.state_dict(), f'{model_dir}/netD_{epoch:03d}.pth')
-            torch.save(optimizerG.state_dict(), f'{model_dir}/optimizerG.pth')
-            torch.save(optimizerD.state_dict(), f'{model_dir}/optimizerD.pth')
-            if ops.loss_scaler_state():          # IEEE-half mode: the dynamic loss scales are optimizer state too
-                torch.save(ops.loss_scaler_state(), f'{model_dir}/loss_scale.pth')
-            if ema is not None:                  # the averaged generator, loadable wherever netG_<epoch>.pth is, and the average's counter
-                torch.save(netG_ema.state_dict(), f'{model_dir}/netG_ema_{epoch:03d}.pth')
-                torch.save(dict(num_updates=int(ema.num_updates.item()), decay=ema.decay, start=ema.start), f'{model_dir}/ema_state.pth')
-            logger.info('Save models')
-            if test_loader is not None:
-                # (--caption_cache: the test split's rows are another table; the train split's encoder carries the test split's)
-                eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder,
-                     netG=netG_ema if ema is not None else netG,
-                     logger=logger, num_samples=6000,
-                     save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None, writer=writer,
-                     eval_opts=eval_opts)
-    flush_saves()                    # the sample grids queued for the writer thread are on disk when train() returns
-    last = _detached(last)
-    if thr is not None:
-        last['throughput'] = thr
-    if graphed is not None:
-        last['hipgraph'] = True
-        graphed.close()
-    return last
+                return finish()
+        clock.after_epoch(nsteps, runner.hipgraph)
+        _end_of_epoch(epoch, last, netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, ema=ema, netG_ema=netG_ema,
+                      fixed=fixed, img_dir=img_dir, model_dir=model_dir, test_loader=test_loader, text_encoder=text_encoder,
+                      logger=logger, writer=writer, eval_opts=eval_opts)
+    return finish()
 
 
 def _detached(last):
@@ -707,7 +824,7 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     cnt, outs = 0, []
     for imgs, texts_lst, keys in loader:
         caps, cap_lens = texts_lst[0]
-        words_embs, sent_embs, mask = text_encoder.forward_keys(keys) if hasattr(text_encoder, 'forward_keys') else text_encoder(caps, cap_lens)
+        words_embs, sent_embs, mask = encode(text_encoder, caps, cap_lens, keys)
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
@@ -756,7 +873,79 @@ def build_models(device):
     return netG, netD, optimizerG, optimizerD
 
 
-def main(argv=None):
+def build_loaders(args, data_dir, device, seed, rank, world, logger):
+    """(train_loader, test_loader or None): ``--synthetic`` batches, the device-resident ``--image_cache``, or the reference's loaders"""
+    if args.synthetic > 0:
+        return SyntheticCOCO(args.synthetic, cfg.TRAIN.BATCH_SIZE, cfg.IMG.SIZE, cfg.TEXT.MAX_LENGTH, seed, cfg.TEXT.VOCA_SIZE), None
+    data_arch = _TEXT_DATASET[cfg.TEXT.TYPE]
+    if args.image_cache:        # the same items out of a device-resident uint8 cache (xmc_gan_amd/imagecache.py): no image is opened here
+        from xmc_gan_amd.imagecache import DeviceImageLoader, ImageCache
+        loaders = {}
+        for mode in ('train', 'test'):
+            text_set = data_arch(data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
+            try:
+                cache = ImageCache.load(args.image_cache, mode, cfg.IMG.SIZE, text_set.filenames, data_dir=data_dir)
+            except ValueError as e:
+                raise SystemExit(f'--image_cache: {e}')       # (the message ends with the command that builds this split's cache)
+            loaders[mode] = DeviceImageLoader(cache, text_set, cfg.TRAIN.BATCH_SIZE, device, train=mode == 'train', seed=args.seed,
+                                              rank=rank, world=world, start_epoch=args.resume_epoch)
+            logger.info(f'image cache {cache.u8_path}: {len(cache)} images, {cache.nbytes} bytes on the device')
+        return loaders['train'], loaders['test']
+    # the reference's loaders (train_gan.py:440-457); each rank draws its own shuffled batches
+    train_set = data_arch(data_dir=data_dir, mode='train', transform=train_transform(cfg.IMG.SIZE), cfg=cfg)
+    test_set = data_arch(data_dir=data_dir, mode='test', transform=test_transform(cfg.IMG.SIZE), cfg=cfg)
+    sampler = torch.utils.data.distributed.DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) \
+        if world > 1 else None
+    train_loader = torch.utils.data.DataLoader(train_set, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True,
+                                               shuffle=sampler is None, sampler=sampler,
+                                               num_workers=int(cfg.TRAIN.NUM_WORKERS), pin_memory=True)
+    test_loader = torch.utils.data.DataLoader(test_set, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=False,
+                                              num_workers=int(cfg.TRAIN.NUM_WORKERS))
+    return train_loader, test_loader
+
+
+def cached_text_encoder(args, data_dir, train_loader, test_loader, device, logger):
+    """``--caption_cache``: the encoder's outputs out of device-resident tables (xmc_gan_amd/captioncache.py), no encoder is constructed;
+    the train split's stand-in carries the test split's as ``eval_encoder``"""
+    from xmc_gan_amd.captioncache import CachedTextEncoder, CaptionCache
+    cached = {}
+    for mode, loader in (('train', train_loader), ('test', test_loader)):
+        text_set = loader.dataset
+        if text_set.transform is not None:      # (the PIL loader's dataset: the same captions, read without its images)
+            text_set = _TEXT_DATASET[cfg.TEXT.TYPE](data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
+        try:
+            c_cache = CaptionCache.load(args.caption_cache, mode, cfg, text_set, ops.precision(), cfg_path=args.cfg)
+        except ValueError as e:
+            raise SystemExit(f'--caption_cache: {e}')     # (the message ends with the command that builds this split's cache)
+        cached[mode] = CachedTextEncoder(c_cache, device)
+        logger.info(f'caption cache {c_cache.f32_path}: {len(c_cache)} captions, {c_cache.nbytes} bytes on the device, {c_cache.encoder} encoder '
+                    f'{c_cache.meta["encoder_fingerprint"]} from {c_cache.meta["encoder_source"]}')
+    cached['train'].eval_encoder = cached['test']
+    return cached['train']
+
+
+def build_text_encoder(device, seed, synthetic=False, sbert_dir='', weights=None):
+    """-> (the frozen text encoder in eval mode, whether it has its weights).  ``weights``: a state dict's path instead of TEXT.ENCODER_DIR;
+    a ``synthetic`` run goes without the latter when the file is not there (random weights: the caller's to broadcast or to warn about)."""
+    if synthetic and cfg.TEXT.ENCODER_NAME != 'RNN':
+        return SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, seed, device), True
+    if cfg.TEXT.ENCODER_NAME == 'SBERT':
+        # frozen weights read from the model directory, the same on every rank: no state dict to load (TEXT.ENCODER_DIR is '' in every
+        # SBERT preset and the reference never loads one), no parameters to broadcast or freeze
+        return SBERT_ENCODER(cfg=cfg, model_dir=sbert_dir or None).to(device).eval(), True
+    text_encoder = _TEXT_ARCH[cfg.TEXT.ENCODER_NAME](cfg=cfg).to(device)        # train_gan.py:459-468
+    path = weights if weights is not None else (f'{PROJ_DIR}/{cfg.TEXT.ENCODER_DIR}' if cfg.TEXT.ENCODER_DIR else '')
+    loaded = bool(path) and (weights is not None or not synthetic or os.path.isfile(path))
+    if loaded:
+        text_encoder.load_state_dict(torch.load(path, map_location=device))
+    for p_ in text_encoder.parameters():
+        p_.requires_grad = False
+    return text_encoder.eval(), loaded
+
+
+def _checked_args(argv):
+    """-> (args, the --diffaug policy, EvalOptions): everything that can be refused before a device is touched; reads the cfg and applies
+    the flags that override it"""
     args = parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0 or args.ema_start < 0:
         raise SystemExit('--ema_decay must be in [0, 1) and --ema_start >= 0')
@@ -782,7 +971,11 @@ def main(argv=None):
         raise SystemExit('--prdc K: 0 (off) or 1 <= K <= 16 nearest neighbours')
     eval_opts = EvalOptions(fid_inception, args.prdc,
                             resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False))
+    return args, aug_policy, eval_opts
 
+
+def _init_process(args):
+    """-> (device, rank, world): this process's card and, under ``torch.distributed.run``, the process group"""
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', str(args.gpu_id)))
     if not torch.cuda.is_available():
@@ -796,8 +989,12 @@ def main(argv=None):
     device = torch.device('cuda', local_rank)
     if world > 1:
         torch.distributed.init_process_group(backend)
-    rank = parallel.rank()
+    return device, parallel.rank(), world
 
+
+def main(argv=None):
+    args, aug_policy, eval_opts = _checked_args(argv)
+    device, rank, world = _init_process(args)
     seed = args.seed + rank
     random.seed(seed)
     np.random.seed(seed)
@@ -814,70 +1011,15 @@ def main(argv=None):
     logger.info(cfg)
     logger.info(f'seed now is : {args.seed}')
 
-    test_loader = None
-    if args.synthetic > 0:
-        train_loader = SyntheticCOCO(args.synthetic, cfg.TRAIN.BATCH_SIZE, cfg.IMG.SIZE, cfg.TEXT.MAX_LENGTH, seed,
-                                     cfg.TEXT.VOCA_SIZE)
-    elif args.image_cache:      # the same items out of a device-resident uint8 cache (xmc_gan_amd/imagecache.py): no image is opened here
-        from xmc_gan_amd.imagecache import DeviceImageLoader, ImageCache
-        data_dir = args.data_dir or f'{PROJ_DIR}/data/{cfg.DATASET_NAME}'
-        data_arch = _TEXT_DATASET[cfg.TEXT.TYPE]
-        loaders = {}
-        for mode in ('train', 'test'):
-            text_set = data_arch(data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
-            try:
-                cache = ImageCache.load(args.image_cache, mode, cfg.IMG.SIZE, text_set.filenames, data_dir=data_dir)
-            except ValueError as e:
-                raise SystemExit(f'--image_cache: {e}')       # (the message ends with the command that builds this split's cache)
-            loaders[mode] = DeviceImageLoader(cache, text_set, cfg.TRAIN.BATCH_SIZE, device, train=mode == 'train', seed=args.seed,
-                                              rank=rank, world=world, start_epoch=args.resume_epoch)
-            logger.info(f'image cache {cache.u8_path}: {len(cache)} images, {cache.nbytes} bytes on the device')
-        train_loader, test_loader = loaders['train'], loaders['test']
-    else:       # the reference's loaders (train_gan.py:440-457); each rank draws its own shuffled batches
-        data_dir = args.data_dir or f'{PROJ_DIR}/data/{cfg.DATASET_NAME}'
-        data_arch = _TEXT_DATASET[cfg.TEXT.TYPE]
-        train_set = data_arch(data_dir=data_dir, mode='train', transform=train_transform(cfg.IMG.SIZE), cfg=cfg)
-        test_set = data_arch(data_dir=data_dir, mode='test', transform=test_transform(cfg.IMG.SIZE), cfg=cfg)
-        sampler = torch.utils.data.distributed.DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) \
-            if world > 1 else None
-        train_loader = torch.utils.data.DataLoader(train_set, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True,
-                                                   shuffle=sampler is None, sampler=sampler,
-                                                   num_workers=int(cfg.TRAIN.NUM_WORKERS), pin_memory=True)
-        test_loader = torch.utils.data.DataLoader(test_set, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=False,
-                                                  num_workers=int(cfg.TRAIN.NUM_WORKERS))
-    if args.caption_cache:      # the encoder's outputs out of device-resident tables (xmc_gan_amd/captioncache.py): no encoder is constructed here
-        from xmc_gan_amd.captioncache import CachedTextEncoder, CaptionCache
-        cached = {}
-        for mode, loader in (('train', train_loader), ('test', test_loader)):
-            text_set = loader.dataset
-            if text_set.transform is not None:      # (the PIL loader's dataset: the same captions, read without its images)
-                text_set = data_arch(data_dir=data_dir, mode=mode, transform=None, cfg=cfg)
-            try:
-                c_cache = CaptionCache.load(args.caption_cache, mode, cfg, text_set, ops.precision(), cfg_path=args.cfg)
-            except ValueError as e:
-                raise SystemExit(f'--caption_cache: {e}')     # (the message ends with the command that builds this split's cache)
-            cached[mode] = CachedTextEncoder(c_cache, device)
-            logger.info(f'caption cache {c_cache.f32_path}: {len(c_cache)} captions, {c_cache.nbytes} bytes on the device, {c_cache.encoder} encoder '
-                        f'{c_cache.meta["encoder_fingerprint"]} from {c_cache.meta["encoder_source"]}')
-        text_encoder = cached['train']
-        text_encoder.eval_encoder = cached['test']
-    elif args.synthetic > 0 and cfg.TEXT.ENCODER_NAME != 'RNN':
-        text_encoder = SyntheticTextEncoder(cfg.TEXT.EMBEDDING_DIM, cfg.TEXT.MAX_LENGTH, seed, device)
-    elif cfg.TEXT.ENCODER_NAME == 'SBERT':
-        # frozen weights read from the model directory, the same on every rank: no state dict to load (TEXT.ENCODER_DIR is '' in every
-        # SBERT preset and the reference never loads one), no parameters to broadcast or freeze
-        text_encoder = SBERT_ENCODER(cfg=cfg, model_dir=args.sbert_dir or None).to(device).eval()
-    else:       # train_gan.py:459-468
-        text_encoder = _TEXT_ARCH[cfg.TEXT.ENCODER_NAME](cfg=cfg).to(device)
-        enc_path = f'{PROJ_DIR}/{cfg.TEXT.ENCODER_DIR}'
-        if cfg.TEXT.ENCODER_DIR != '' and (args.synthetic <= 0 or os.path.isfile(enc_path)):
-            text_encoder.load_state_dict(torch.load(enc_path, map_location=device))
-        elif world > 1:     # random (synthetic-run) encoder weights must agree across ranks
+    data_dir = args.data_dir or f'{PROJ_DIR}/data/{cfg.DATASET_NAME}'
+    train_loader, test_loader = build_loaders(args, data_dir, device, seed, rank, world, logger)
+    if args.caption_cache:
+        text_encoder = cached_text_encoder(args, data_dir, train_loader, test_loader, device, logger)
+    else:
+        text_encoder, has_weights = build_text_encoder(device, seed, args.synthetic > 0, args.sbert_dir)
+        if not has_weights and world > 1:       # random (synthetic-run) encoder weights must agree across ranks
             for p_ in text_encoder.parameters():
                 torch.distributed.broadcast(p_.data, 0)
-        for p_ in text_encoder.parameters():
-            p_.requires_grad = False
-        text_encoder.eval()
 
     netG, netD, optimizerG, optimizerD = build_models(device)
     if world > 1:   # same initial weights (and spectral-norm u/v vectors, which then evolve identically) on every rank
@@ -888,13 +1030,7 @@ def main(argv=None):
 
     state_epoch = args.resume_epoch
     if state_epoch != 0:
-        netG.load_state_dict(torch.load(f'{model_dir}/netG_{state_epoch:03d}.pth', map_location=device))
-        netD.load_state_dict(torch.load(f'{model_dir}/netD_{state_epoch:03d}.pth', map_location=device))
-        optimizerG.load_state_dict(torch.load(f'{model_dir}/optimizerG.pth', map_location=device))
-        optimizerD.load_state_dict(torch.load(f'{model_dir}/optimizerD.pth', map_location=device))
-        if os.path.isfile(f'{model_dir}/loss_scale.pth'):
-            ops.load_loss_scaler_state(torch.load(f'{model_dir}/loss_scale.pth', map_location='cpu'), device)
-        logger.info(f'Load models, epoch : {state_epoch}')
+        load_checkpoint(model_dir, state_epoch, netG, netD, optimizerG, optimizerD, device=device, logger=logger)
     elif cfg.DISC.ENCODER_DIR:
         netD.load_state_dict(torch.load(f'{PROJ_DIR}/{cfg.DISC.ENCODER_DIR}', map_location=device), strict=False)
 
@@ -904,14 +1040,7 @@ def main(argv=None):
         ema = ParamEMA(netG, args.ema_decay, args.ema_start)
         logger.info(f'generator weight EMA: decay {ema.decay}, averaging after {ema.start} generator steps')
         if state_epoch != 0:
-            f_w, f_s = f'{model_dir}/netG_ema_{state_epoch:03d}.pth', f'{model_dir}/ema_state.pth'
-            if os.path.isfile(f_w) and os.path.isfile(f_s):
-                saved = torch.load(f_s, map_location='cpu')
-                ema.load_state_dict(dict(shadow=torch.load(f_w, map_location=device), num_updates=saved['num_updates']))
-                logger.info(f'Load EMA generator, epoch : {state_epoch} ({saved["num_updates"]} updates; saved with decay '
-                            f'{saved["decay"]}, start {saved["start"]})')
-            else:
-                logger.info(f'no netG_ema_{state_epoch:03d}.pth / ema_state.pth in {model_dir}: the EMA starts from netG_{state_epoch:03d}.pth')
+            load_average(model_dir, state_epoch, ema, device, logger)
 
     # augmentation of the discriminator's inputs (--diffaug): one sampler, created before any capture.  Its draws come from (seed, rank) and,
     # on a resume, from (seed, rank, epoch): a resumed run does not continue the interrupted run's draws, it starts a stream of its own
