@@ -54,7 +54,8 @@ extern "C" {
  *     xmc_crop_flip_normalize (csrc/datafeed.hip);
  *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass);
  *     xmc_caption_gather (csrc/captionfeed.hip);
- *     xmc_manifold_slices / xmc_row_sqnorm / xmc_knn_radius2 / xmc_manifold_count (csrc/manifold.hip). */
+ *     xmc_manifold_slices / xmc_row_sqnorm / xmc_knn_radius2 / xmc_manifold_count (csrc/manifold.hip);
+ *     xmc_poly_mmd_tiles / xmc_poly_mmd_sums / xmc_inception_score_ws_bytes / xmc_inception_score (csrc/kid.hip). */
 #define XMC_ABI_VERSION 12
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -805,6 +806,40 @@ int xmc_row_sqnorm(const float* x, float* n2, int N, int D, void* stream);
 int xmc_knn_radius2(const float* x, const float* n2, float* r2, float* ws, int64_t ws_bytes, int N, int D, int k, int slices, void* stream);
 int xmc_manifold_count(const float* a, const float* na2, const float* b, const float* nb2, const float* rb2, int32_t* count, float* near2,
                        void* ws, int64_t ws_bytes, int Na, int Nb, int D, int slices, void* stream);
+
+/* ---- Kernel Inception Distance and Inception Score (csrc/kid.hip; xmc_gan_amd/manifold.py `kid`, xmc_gan_amd/fid.py `InceptionScore`) ---
+ * poly_mmd_sums: the three kernel sums of the unbiased MMD^2 estimate with k(x, y) = (x.y / D + 1)^3, for S subsets of m rows per side in
+ * ONE launch.  real f32 [Nr,D], fake f32 [Nf,D]; idx_real / idx_fake int32 [S,m]: the rows of each subset (every entry in [0, Nr) /
+ * [0, Nf): the CALLER checks that; whatever it is handed, the kernel reads at an index clamped into the bank).
+ *   out f64 [S,3]:  out[s][0] = sum over ordered pairs i != j of k(X_i, X_j), X_i = real[idx_real[s][i]]   (m (m - 1) terms)
+ *                   out[s][1] = the same over Y_i = fake[idx_fake[s][i]]
+ *                   out[s][2] = sum over all m^2 pairs of k(X_i, Y_j)
+ * The diagonal is left out by POSITION in the subset: two positions that name one bank row are a pair.  The dot products are 128 x 128
+ * blocks of the f32-input MFMA, rows gathered through the index table while they are staged (no gathered copy of a subset exists), one fma
+ * chain over D in a fixed column order, D never split.  Per element t = fmaf(dot, 1/D, 1), t*t*t in f32, widened to f64 and added to a
+ * per-lane f64 sum.  Only the upper tiles of the two within-set Grams are computed, the strictly upper ones counted twice.  Every tile
+ * writes one f64 partial to `ws`; a second launch adds a sum's partials in tile order.  No atomics: the same bytes from run to run.
+ *   tiles: the number of f64 partials per subset (ws holds S * tiles doubles); host only; 0 when m < 1.
+ * XMC_EINVAL: a NULL pointer, Nr / Nf < 1, S < 1 or S > 65535, ws_bytes too small.  XMC_ESHAPE: D % 4 != 0, D < 4, D > 4096, m < 2,
+ * m > 2^20.  XMC_EALIGN: real / fake not 16-byte aligned, out / ws not 8-byte aligned.  All refused before any launch.
+ *
+ * inception_score: logits f32 [N,C] with a row stride of ld floats (ld >= C: columns C..ld-1 are never read).  The rows are cut into
+ * `splits` consecutive parts, part s = rows [s N / splits, (s + 1) N / splits).  With p(y|x) = softmax of a row:
+ *   H f64 [splits]:    H[s]    = sum over the part's rows and all classes of p log p
+ *   P f64 [splits,C]:  P[s][y] = sum over the part's rows of p(y|x)
+ * Everything after the load is f64: the row maximum is subtracted, then exp, log and the sums.  64 consecutive rows of a part belong to
+ * one workgroup, 16 to each of its waves in order; the workgroups' partials go to `ws` and a second launch adds them in order.  No atomics.
+ * The host finishes: IS_s = exp(H[s] / n_s - sum_y pbar log pbar), pbar = P[s] / n_s.
+ *   ws_bytes: what `ws` must hold; host only; 0 for arguments the call would refuse.
+ * XMC_EINVAL: a NULL pointer, N < 1, splits < 1, splits > N or splits > 65535 (a grid dimension), ld < C, ws_bytes too small.
+ * XMC_ESHAPE: C < 1, C > 1024, N > 2^30.
+ * XMC_EALIGN: logits not 4-byte, H / P / ws not 8-byte aligned.  All refused before any launch. */
+int xmc_poly_mmd_tiles(int m);
+int xmc_poly_mmd_sums(const float* real, const float* fake, const int32_t* idx_real, const int32_t* idx_fake, double* out, double* ws,
+                      int64_t ws_bytes, int Nr, int Nf, int D, int S, int m, void* stream);
+int64_t xmc_inception_score_ws_bytes(int N, int C, int splits);
+int xmc_inception_score(const float* logits, int64_t ld, double* H, double* P, double* ws, int64_t ws_bytes, int N, int C, int splits,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,10 @@
 """The evaluation pipeline behind ``train_gan.eval()``, ``sample.py`` and the scoring command lines ("The evaluation pipeline"):
-where a metric's weights come from, the loaded models, and ``MetricSuite`` -- FID, precision / recall / density / coverage (PRDC) and
-R-precision over one pass of the images.  Nothing but ``os`` is imported until a metric is asked for."""
+where a metric's weights come from, the loaded models, and ``MetricSuite`` -- FID, precision / recall / density / coverage (PRDC),
+R-precision, KID and the Inception Score over one pass of the images.  Nothing but ``os`` is imported until a metric is asked for."""
 import os
 
-FID, PRDC, RPREC = "FID", "PRDC", "R-precision"
-CACHE_FILES = {FID: "org_stats.npz", PRDC: "org_features.npz"}       # eval()'s real side, beside org_dir
+FID, PRDC, RPREC, KID, IS = "FID", "PRDC", "R-precision", "KID", "IS"
+CACHE_FILES = {FID: "org_stats.npz", PRDC: "org_features.npz", KID: "org_features.npz"}       # eval()'s real side, beside org_dir (PRDC and KID: one file)
 _WHAT = {"XMC_FID_INCEPTION": "FID Inception weights", "XMC_DAMSM_IMAGE_ENCODER": "DAMSM image encoder weights"}
 _models = {}            # 'inception' / 'damsm' -> (key, model): one loaded model per kind (`load_model`)
 
@@ -52,14 +52,19 @@ class MetricSuite:
     The generated side comes through ``update_fake``; the real side of FID and PRDC from ``update_real`` while ``wants_real``, from
     ``real_from_path``, or from the cache files that ``open_cache`` reads and ``real_from_cache`` settles.  The cache rule: a file is reused
     if and only if it was made from as many images as were generated now; otherwise the real side is the rows ``update_real`` gathered -- or,
-    where a file for another count kept them from being gathered, those of one more pass over the real images -- and is written."""
+    where a file for another count kept them from being gathered, those of one more pass over the real images -- and is written.
+    ``kid``: the Kernel Inception Distance over ``kid_subsets`` subsets of ``kid_subset_size`` rows; it is two-sided, takes the feature rows
+    and shares PRDC's bank and cache file: with both on, the rows are stored, read and written once.  ``inception_score`` > 0: the Inception
+    Score over that many splits, one-sided like R-precision."""
 
-    def __init__(self, device, fid_inception="", prdc_k=0, damsm_image_encoder="", text_encoder=None, rp_k=100, rp_splits=10, rp_seed=0, fid=True):
+    def __init__(self, device, fid_inception="", prdc_k=0, damsm_image_encoder="", text_encoder=None, rp_k=100, rp_splits=10, rp_seed=0, fid=True,
+                 kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0, inception_score=0):
         self.device, self.prdc_k, self.why = device, int(prdc_k), {}
+        self.kid_args, is_splits = (int(kid_subsets), int(kid_subset_size), int(kid_seed)), int(inception_score)
         self.extractor = self.encoder = self._cache_dir = None
         self.fake = {}                                              # metric -> its accumulator of the generated side: the metrics that are on
         self._gathered, self._cached, self.real = {}, {}, {}        # FID / PRDC -> real accumulator; (what a cache file held, n); () -> real side
-        if fid_inception and (fid or self.prdc_k > 0):
+        if fid_inception and (fid or self.prdc_k > 0 or kid or is_splits > 0):
             self.extractor = load_model("inception", fid_inception, device)
             if fid:
                 from .fid import FeatureStats
@@ -67,8 +72,19 @@ class MetricSuite:
             if self.prdc_k > 0:
                 from .manifold import FeatureBank
                 self.fake[PRDC] = FeatureBank(device=device)
-        elif self.prdc_k > 0:
-            self.why[PRDC] = "it takes the Inception features of FID: --fid_inception PATH or XMC_FID_INCEPTION"
+            if kid:
+                from .manifold import FeatureBank
+                self.fake[KID] = self.fake[PRDC] if PRDC in self.fake else FeatureBank(device=device)       # one bank of rows for both
+            if is_splits > 0:
+                from .fid import InceptionScore
+                try:
+                    self.fake[IS] = InceptionScore(self.extractor, is_splits, device)
+                except ValueError as e:                     # (the weights file holds no classifier)
+                    self.why[IS] = str(e)
+        else:
+            for m, on in ((PRDC, self.prdc_k > 0), (KID, kid), (IS, is_splits > 0)):
+                if on:
+                    self.why[m] = "it takes the Inception features of FID: --fid_inception PATH or XMC_FID_INCEPTION"
         if damsm_image_encoder:
             from . import rprecision as RP
             self.encoder = load_model("damsm", damsm_image_encoder, device)
@@ -77,7 +93,8 @@ class MetricSuite:
                 self.fake[RPREC] = RP.RPrecision(rp_k, rp_splits, rp_seed)
             else:
                 self.why[RPREC] = why
-        self._two_sided = [m for m in (FID, PRDC) if m in self.fake]
+        self._rows = PRDC if PRDC in self.fake else KID                # the metric the bank of rows and its real side are kept under
+        self._two_sided = [m for m in (FID, self._rows) if m in self.fake]
 
     def _u8(self, images):
         """[B,3,H,W] floats in [-1, 1] -> the uint8 [B,H,W,3] the PNGs hold; uint8 images are taken as they are"""
@@ -97,9 +114,9 @@ class MetricSuite:
         if not self.fake:
             return
         u8 = self._u8(images)
-        if self._two_sided:
+        if self._two_sided or IS in self.fake:
             feats = self.extractor(u8)
-            for m in self._two_sided:
+            for m in self._two_sided + [IS] * (IS in self.fake):
                 self.fake[m].update(feats)
         if RPREC in self.fake:
             self.fake[RPREC].update(self.encoder.encode_u8(u8)[1], sent_embs, caption_of_image)
@@ -114,14 +131,23 @@ class MetricSuite:
         if self.wants_real:
             self._feed_real(images, self.wants_real)
 
-    def real_from_path(self, fid_path=None, prdc_path=None, batch=100):
-        """FID's real side (an image directory or an .npz statistics file) and PRDC's (a directory or a feature file), read by ``results()``"""
+    def real_from_path(self, fid_path=None, prdc_path=None, batch=100, kid_path=None):
+        """FID's real side (an image directory or an .npz statistics file), PRDC's and KID's (a directory or a feature file each; the same
+        path is read once), read by ``results()``"""
         if FID in self.fake:
             from .fid import stats_of
             self.real[FID] = lambda: stats_of(fid_path, self.extractor, batch)
-        if PRDC in self.fake:
+        banks = {}
+
+        def bank(path):
             from .manifold import bank_of
-            self.real[PRDC] = lambda: bank_of(prdc_path, self.extractor, batch, self.device)
+            if path not in banks:
+                banks[path] = bank_of(path, self.extractor, batch, self.device)
+            return banks[path]
+        if PRDC in self.fake:
+            self.real[PRDC] = lambda: bank(prdc_path)
+        if KID in self.fake:
+            self.real[KID] = lambda: bank(kid_path)
 
     def open_cache(self, cache_dir):
         """before the first batch: ``cache_dir`` holds (or will hold) the real side's files; a feature file that does not read counts as absent"""
@@ -160,15 +186,22 @@ class MetricSuite:
         from . import manifold as MF          # (`prdc` is looked up on the module when it is called)
         return MF.prdc(self.real[PRDC](), self.fake[PRDC], self.prdc_k)
 
+    def _kid(self):
+        from . import manifold as MF
+        subsets, size, seed = self.kid_args
+        return MF.kid(self.real[KID if KID in self.real else self._rows](), self.fake[KID], subsets, size, seed)
+
     def results(self):
-        """yields (metric, values or None, why not or None) for every metric asked for, in the order FID, PRDC, R-precision; values: dict(FID=x),
-        `manifold.prdc`'s dict, `RPrecision.finalize`'s dict.  A ValueError of theirs is the reason."""
+        """yields (metric, values or None, why not or None) for every metric asked for, in the order FID, PRDC, R-precision, KID, IS; values:
+        dict(FID=x), `manifold.prdc`'s dict, `RPrecision.finalize`'s dict, `manifold.kid`'s dict, `InceptionScore.finalize`'s dict.  A
+        ValueError of theirs is the reason."""
         if FID in self.fake and self.fake[FID].n < 2:
             yield FID, None, "fewer than two images"
         elif FID in self.fake:
             from .fid import frechet_distance
             yield FID, dict(FID=frechet_distance(*self.real[FID](), *self.fake[FID].finalize())), None
-        for metric, compute in ((PRDC, self._prdc), (RPREC, lambda: self.fake[RPREC].finalize())):
+        for metric, compute in ((PRDC, self._prdc), (RPREC, lambda: self.fake[RPREC].finalize()), (KID, self._kid),
+                                (IS, lambda: self.fake[IS].finalize())):
             values, why = None, self.why.get(metric)
             if metric in self.fake:
                 try:

@@ -23,6 +23,8 @@ from .ops import ConvGeom, _conv_fwd_raw
 
 BN_EPS = 1e-3
 DIMS = 2048
+CLASSES = 1008            # the outputs of the 2015 Inception's ``fc``: all of them enter the Inception Score
+IS_SPLITS = 10
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg")
 
 
@@ -126,6 +128,21 @@ def load_inception_weights(path=None):
     return check_inception_state(sd, "InceptionFID", path)
 
 
+def load_inception_fc(path=None):
+    """``fc.weight`` f32 [1008, 2048] of the same file `load_inception_weights` reads (the classifier of the Inception Score; its bias is
+    not used).  ImportError: no path or no file; ValueError: the file holds no such tensor, or one of another shape."""
+    path = path or os.environ.get("XMC_FID_INCEPTION", "")
+    if not path or not os.path.isfile(path):
+        raise ImportError(f"the Inception Score needs the FID Inception weights file, got {path!r}")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    w = sd.get("fc.weight") if isinstance(sd, dict) else None
+    if w is None:
+        raise ValueError(f"the weights in {path} hold no 'fc.weight' (the [{CLASSES}, {DIMS}] classifier the Inception Score takes its logits from)")
+    if tuple(w.shape) != (CLASSES, DIMS):
+        raise ValueError(f"fc.weight in {path} is {tuple(w.shape)}, the Inception Score needs [{CLASSES}, {DIMS}]")
+    return w.detach().to(torch.float32).contiguous()
+
+
 def conv_bias_relu(x, w, b, geom):
     """relu(conv(x, w) + b) in f32 on the generic implicit-GEMM kernel: x f32 [N,H,W,cin (3 -> 8)], w [cout,cin,kh,kw], b f32 [cout].
     A kernel of more than MAX_TAPS taps (the 5x5 layers: 25) runs as tap ranges, each added to the one before in f32, then the ReLU."""
@@ -223,6 +240,25 @@ class InceptionFID(InceptionTrunk):
     def __init__(self, weights=None, device="cuda", resize_to=299):
         super().__init__(load_inception_weights(weights), device, "fid")
         self.resize_to = resize_to
+        self._weights, self._fc = weights, None
+
+    def fc(self):
+        """(geometry, weight) of the classifier as a 1x1 convolution: read from the weights file at the first call (`load_inception_fc`)"""
+        if self._fc is None:
+            w = load_inception_fc(self._weights).reshape(CLASSES, DIMS, 1, 1)
+            self._fc = ConvGeom(DIMS, CLASSES, 1, 1, 0), torch.nn.Parameter(w.to(self.device).contiguous(), requires_grad=False)
+        return self._fc
+
+    @torch.no_grad()
+    def logits(self, features):
+        """pool3 rows f32 [N,2048] -> the 1008 logits f32 [N,1008] = features @ fc.weight.T, WITHOUT the bias (as the original Inception
+        Score code and torch-fidelity take them): a 1x1 convolution on a 1x1 map, on the f32 implicit-GEMM path of the trunk"""
+        f = ops._fid_arg(torch.as_tensor(features).to(self.device), "InceptionFID.logits", torch.float32, 2)
+        if f.shape[1] != DIMS or f.shape[0] < 1:
+            raise ValueError(f"InceptionFID.logits: feature rows [N,{DIMS}] expected, got {tuple(f.shape)}")
+        geom, w = self.fc()
+        y = _conv_fwd_raw(f.view(f.shape[0], 1, 1, DIMS), w, None, geom, L.ACT_NONE, torch.float32)
+        return y.view(f.shape[0], -1)[:, :CLASSES]           # (1008 is a multiple of 8: the stored row has no padding column)
 
     @torch.no_grad()
     def __call__(self, u8):
@@ -276,6 +312,54 @@ class FeatureStats:
         mu, sigma = self.finalize()
         save_stats(path, mu, sigma, self.n)
         return mu, sigma
+
+
+def is_split_bounds(n, splits):
+    """the parts of the Inception Score: [(s n // splits, (s + 1) n // splits)] -- consecutive rows in order of arrival, no shuffling"""
+    n, splits = int(n), int(splits)
+    if splits < 1 or n < splits:
+        raise ValueError(f"the Inception Score over {splits} splits needs at least that many images, got {n}")
+    return [(s * n // splits, (s + 1) * n // splits) for s in range(splits)]
+
+
+def is_from_sums(H, P, n, splits):
+    """(mean, std with ddof 0, the per-part scores) from `ops.inception_score_sums`' H [splits] and P [splits,C], in f64 on the host:
+    part s scores exp(H_s / n_s - sum_y pbar log pbar), pbar = P_s / n_s (the mean KL divergence of p(y|x) from the part's marginal)"""
+    H, P = np.asarray(H, np.float64), np.asarray(P, np.float64)
+    scores = []
+    for s, (lo, hi) in enumerate(is_split_bounds(n, splits)):
+        pbar = P[s] / (hi - lo)
+        pos = pbar > 0
+        scores.append(np.exp(H[s] / (hi - lo) - float(np.sum(pbar[pos] * np.log(pbar[pos])))))
+    scores = np.asarray(scores, np.float64)
+    return float(scores.mean()), float(scores.std()), scores
+
+
+class InceptionScore:
+    """Inception Score (Salimans et al. 2016) of generated images: ``update(features)`` takes pool3 rows [B,2048] and keeps their 1008
+    logits (`InceptionFID.logits`: no bias) in a `manifold.FeatureBank`; ``finalize()`` cuts them into ``splits`` consecutive parts and
+    returns dict(inception_score, std, splits, n): mean and standard deviation (ddof 0) over the parts of exp(E_x KL(p(y|x) || p_s(y)))."""
+
+    def __init__(self, extractor, splits=IS_SPLITS, device=None):
+        from .manifold import FeatureBank
+        self.extractor, self.splits = extractor, int(splits)
+        if self.splits < 1:
+            raise ValueError(f"InceptionScore: {splits} splits")
+        extractor.fc()                                        # (a file without the classifier is refused here, not after the images)
+        self.bank = FeatureBank(CLASSES, device or extractor.device)
+
+    @property
+    def n(self):
+        return self.bank.n
+
+    def update(self, features):
+        self.bank.update(self.extractor.logits(features))
+
+    def finalize(self):
+        is_split_bounds(self.n, self.splits)
+        H, P = ops.inception_score_sums(self.bank.rows(), self.splits)
+        mean, std, _ = is_from_sums(H.cpu().numpy(), P.cpu().numpy(), self.n, self.splits)
+        return dict(inception_score=mean, std=std, splits=self.splits, n=int(self.n))
 
 
 def save_stats(path, mu, sigma, n=None):

@@ -188,8 +188,13 @@ _SIGS = {
     "xmc_row_sqnorm": [vp, vp, i32, i32, vp],
     "xmc_knn_radius2": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
     "xmc_manifold_count": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "xmc_poly_mmd_tiles": [i32],
+    "xmc_poly_mmd_sums": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
+    "xmc_inception_score_ws_bytes": [i32, i32, i32],
+    "xmc_inception_score": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
 }
-_RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p}
+_RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p,
+            "xmc_inception_score_ws_bytes": i64}
 EXPORTS = tuple(_SIGS)
 
 _libs = {}               # variant -> loaded library

@@ -13,6 +13,15 @@ With d2(a, b) = |a - b|^2, R [Nr, D] real rows, G [Ng, D] generated rows:
 
 ``FeatureBank`` keeps rows on the device; ``prdc`` runs two radius and two count launches (the N x N matrix exists nowhere) and reduces the
 per-row results on the host in f64; ``prdc_from_counts`` is that host reduction alone.
+
+``kid`` is the Kernel Inception Distance (Binkowski et al. 2018) of the same rows, on csrc/kid.hip: the polynomial kernel
+k(x, y) = (x.y / D + 1)^3 and, over ``subsets`` subsets of m = min(subset_size, Nr, Ng) rows per side drawn without replacement
+(``kid_subsets``), the unbiased
+
+    MMD^2 = (sum_{i != j} k(X_i, X_j) + sum_{i != j} k(Y_i, Y_j)) / (m (m - 1)) - 2 sum_{i, j} k(X_i, Y_j) / m^2
+
+whose mean and standard deviation (ddof 0) over the subsets are reported.  The kernel, the subset count and size are torch-fidelity's
+defaults; the draw is this project's own, so a value differs from torch-fidelity's by sampling noise only -- the noise ``std`` shows.
 """
 import os
 
@@ -120,6 +129,47 @@ def prdc(real, fake, k=5):
     cnt_g, _ = ops.manifold_count(fake, real, rad2_r)
     cnt_r, near2_r = ops.manifold_count(real, fake, rad2_g)
     return prdc_from_counts(cnt_g.cpu().numpy(), cnt_r.cpu().numpy(), near2_r.cpu().numpy(), rad2_r.cpu().numpy(), k)
+
+
+KID_SUBSETS, KID_SUBSET_SIZE = 100, 1000
+
+
+def kid_subsets(n_real, n_fake, subsets=KID_SUBSETS, size=KID_SUBSET_SIZE, seed=0):
+    """the subsets of KID: two int32 [subsets, m] tables of rows, m = min(size, n_real, n_fake), every row of a table drawn without
+    replacement.  One generator, ``np.random.default_rng([seed, 0x4B4944])``; per subset the real indices first, then the generated ones.
+    ValueError: m < 2 or subsets < 1."""
+    n_real, n_fake, subsets, size = int(n_real), int(n_fake), int(subsets), int(size)
+    m = min(size, n_real, n_fake)
+    if m < 2:
+        raise ValueError(f"KID needs at least two rows per side and subset, got {n_real} real and {n_fake} generated rows at subset size {size}")
+    if subsets < 1:
+        raise ValueError(f"KID: {subsets} subsets")
+    rng = np.random.default_rng([int(seed), 0x4B4944])
+    idx_r, idx_f = np.empty((subsets, m), np.int32), np.empty((subsets, m), np.int32)
+    for s in range(subsets):
+        idx_r[s] = rng.choice(n_real, m, replace=False)
+        idx_f[s] = rng.choice(n_fake, m, replace=False)
+    return idx_r, idx_f
+
+
+def kid_from_sums(sums, m):
+    """(mean, std with ddof 0) over the subsets of the unbiased MMD^2 from the [S,3] sums of `ops.poly_mmd_sums`, in f64 on the host"""
+    sums, m = np.asarray(sums, np.float64), int(m)
+    mmd2 = (sums[:, 0] + sums[:, 1]) / (m * (m - 1.0)) - 2.0 * sums[:, 2] / (float(m) * m)
+    return float(mmd2.mean()), float(mmd2.std())
+
+
+def kid(real, fake, subsets=KID_SUBSETS, subset_size=KID_SUBSET_SIZE, seed=0):
+    """Kernel Inception Distance of ``fake`` against ``real`` (f32 [N,D] device tensors or `FeatureBank`s; D % 4 == 0, 4 <= D <= 4096)
+    -> dict(kid, std, subsets, subset_size, n_real, n_fake); ``subset_size`` is the m that was used.  ValueError: fewer than two rows."""
+    real, fake = _rows(real), _rows(fake)
+    if real.dim() != 2 or fake.dim() != 2 or real.shape[1] != fake.shape[1]:
+        raise ValueError(f"kid: feature rows [Nr,D] and [Ng,D] expected, got {tuple(real.shape)} and {tuple(fake.shape)}")
+    idx_r, idx_f = kid_subsets(real.shape[0], fake.shape[0], subsets, subset_size, seed)
+    m = idx_r.shape[1]
+    sums = ops.poly_mmd_sums(real, fake, torch.from_numpy(idx_r), torch.from_numpy(idx_f))
+    mean, std = kid_from_sums(sums.cpu().numpy(), m)
+    return dict(kid=mean, std=std, subsets=int(idx_r.shape[0]), subset_size=int(m), n_real=int(real.shape[0]), n_fake=int(fake.shape[0]))
 
 
 def bank_of_dir(directory, extractor, batch=100):

@@ -647,6 +647,55 @@ def manifold_count(a, b, rb2, slices=0):
     return count, near2
 
 
+# ------------------------------------------------------------------------------------------ KID / Inception Score (csrc/kid.hip): outside autograd
+def _index_table(what, idx, n, device):
+    """an int32 [S,m] table of rows of a bank of ``n`` rows, checked against [0, n) HERE, on the host, before anything is launched"""
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 2 or idx.dtype != torch.int32 or idx.shape[0] < 1:
+        raise ValueError(f"{what}: an int32 [S,m] index table expected, got {idx.dtype} {tuple(idx.shape)}")
+    if idx.numel():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{what}: the indices span [{lo}, {hi}], the bank has {n} rows")
+    return idx.to(device).contiguous()
+
+
+def poly_mmd_sums(real, fake, idx_real, idx_fake):
+    """The kernel sums of KID's unbiased MMD^2, k(x, y) = (x.y / D + 1)^3, for S subsets of m rows per side in one launch: real f32 [Nr,D],
+    fake f32 [Nf,D], idx_real / idx_fake int32 [S,m] (rows of the banks, checked against them on the host) -> f64 [S,3]: the sum of k over
+    the ordered pairs i != j (by POSITION in the subset) of the real subset, the same of the generated one, and the sum over all m^2 cross
+    pairs.  D % 4 == 0, 4 <= D <= 4096, m >= 2.  No m x m matrix and no gathered copy of a subset is stored; the same bytes every run."""
+    real, fake = _fid_arg(real, "poly_mmd_sums", torch.float32, 2), _fid_arg(fake, "poly_mmd_sums", torch.float32, 2)
+    D = _manifold_dims("poly_mmd_sums", real, fake)
+    ir, jf = _index_table("poly_mmd_sums", idx_real, real.shape[0], real.device), _index_table("poly_mmd_sums", idx_fake, fake.shape[0], real.device)
+    (S, m) = ir.shape
+    if tuple(jf.shape) != (S, m) or m < 2 or S > 65535:
+        raise ValueError(f"poly_mmd_sums: index tables {tuple(ir.shape)} and {tuple(jf.shape)}; two [S,m] tables with m >= 2 and S <= 65535 expected")
+    tiles = getattr(L.load(), "xmc_poly_mmd_tiles")(m)
+    out = torch.empty((S, 3), dtype=torch.float64, device=real.device)
+    ws = torch.empty((S * tiles,), dtype=torch.float64, device=real.device)
+    L.call("xmc_poly_mmd_sums", _p(real), _p(fake), _p(ir), _p(jf), _p(out), _p(ws), ws.numel() * 8, real.shape[0], fake.shape[0], D, S, m, _st())
+    return out
+
+
+def inception_score_sums(logits, splits, classes=None):
+    """logits f32 [N,ld] (``classes``: only the first that many columns are logits, the others are never read) cut into ``splits``
+    consecutive parts [s N // splits, (s + 1) N // splits) -> (H f64 [splits], P f64 [splits,C]): per part the sum of p log p over rows and
+    classes and the per-class sum of p over rows, p = softmax(row), everything in f64 and in a fixed order.  C <= 1024, 1 <= splits <= N."""
+    _need_cuda(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.requires_grad or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"inception_score_sums: f32 logits [N,C] with unit column stride expected, got {logits.dtype} {tuple(logits.shape)}")
+    N, C, splits = logits.shape[0], int(logits.shape[1] if classes is None else classes), int(splits)
+    if not 1 <= C <= min(1024, logits.shape[1]) or not 1 <= splits <= min(N, 65535):
+        raise ValueError(f"inception_score_sums: {N} rows, {C} of {logits.shape[1]} columns, {splits} splits; 1 <= C <= 1024 and 1 <= splits <= N expected")
+    H = torch.empty((splits,), dtype=torch.float64, device=logits.device)
+    P = torch.empty((splits, C), dtype=torch.float64, device=logits.device)
+    nbytes = getattr(L.load(), "xmc_inception_score_ws_bytes")(N, C, splits)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=logits.device)
+    L.call("xmc_inception_score", _p(logits), logits.stride(0), _p(H), _p(P), _p(ws), nbytes, N, C, splits, _st())
+    return H, P
+
+
 # ------------------------------------------------------------------------------------------ differentiable augmentation
 def _diffaug_raw(x, params, cut, color, channels, transposed, linear_only):
     """one sums launch (only with a colour component) and one apply launch of csrc/augment.hip"""

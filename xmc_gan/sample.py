@@ -5,6 +5,7 @@
                              [--best_of M --netD netD_*.pth] [--walk N] [--interp_sent N] [--grid_max N] [--no_png]
                              [--fid_against DIR_OR_NPZ --fid_inception PATH] [--prdc_against DIR_OR_FEATURES_NPZ [--prdc_k K]]
                              [--rprecision --damsm_image_encoder PATH]
+                             [--kid_against DIR_OR_FEATURES_NPZ [--kid_subsets S --kid_subset_size M]] [--inception_score [--is_splits S]]
 
 Writes ``<out>/<caption index:05d>_<k>.png`` (K images per caption), ``<out>/grid.png`` (the first ``--grid_max`` of them, every image min-max scaled
 on its own like the trainer's sample grids), ``<out>/captions.txt`` and ``<out>/manifest.json``.  The generator runs on the HIP kernels of
@@ -67,6 +68,15 @@ def parse_args(argv=None):
                         help='score the sampled images: precision / recall / density / coverage against an image directory or an .npz feature '
                              'file (xmc_gan/prdc.py --save_features) -> manifest "prdc"; takes --fid_inception')
     parser.add_argument('--prdc_k', type=int, default=5, metavar='K', help='--prdc_against: nearest neighbours (1..16)')
+    parser.add_argument('--kid_against', type=str, default='', metavar='DIR_OR_FEATURES_NPZ',
+                        help='Kernel Inception Distance of the sampled images against an image directory or an .npz feature file '
+                             '-> manifest "kid"; takes --fid_inception.  The subsets are drawn with --seed (default 100): '
+                             'xmc_gan/kid.py gives the same value with --seed set to that')
+    parser.add_argument('--kid_subsets', type=int, default=100, metavar='S', help='--kid_against: the number of subsets')
+    parser.add_argument('--kid_subset_size', type=int, default=1000, metavar='M', help='--kid_against: rows per side of a subset (at most)')
+    parser.add_argument('--inception_score', action='store_true',
+                        help='Inception Score of the sampled images -> manifest "inception_score"; takes --fid_inception')
+    parser.add_argument('--is_splits', type=int, default=10, metavar='S', help='--inception_score: consecutive parts the mean and its spread are taken over')
     parser.add_argument('--rprecision', action='store_true',
                         help='score the sampled images: R-precision against their captions (RNN presets) -> manifest "r_precision"')
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
@@ -104,14 +114,22 @@ def _check_args(args):
         raise SystemExit('--walk / --interp_sent need at least 2 frames')
     if args.walk and max(args.n_per_caption, args.best_of) < 2:
         raise SystemExit("--walk goes from a caption's first noise to its second: ask for --n_per_caption 2 (or more)")
-    for flag, path, holds in (('--fid_against', args.fid_against, 'statistics'), ('--prdc_against', args.prdc_against, 'feature')):
+    for flag, path, holds in (('--fid_against', args.fid_against, 'statistics'), ('--prdc_against', args.prdc_against, 'feature'),
+                              ('--kid_against', args.kid_against, 'feature')):
         if path:
             if image_set_kind(path) is None:
                 raise SystemExit(f'{flag}: {path} is neither an image directory nor an .npz {holds} file')
             if flag == '--prdc_against' and not 1 <= args.prdc_k <= 16:
                 raise SystemExit(f'--prdc_k: {args.prdc_k}; 1 <= K <= 16 expected')
+            if flag == '--kid_against' and (args.kid_subsets < 1 or args.kid_subset_size < 2):
+                raise SystemExit(f'--kid_subsets {args.kid_subsets} / --kid_subset_size {args.kid_subset_size}: S >= 1 and M >= 2 expected')
             args.fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception',
                                                  refusal=f'{flag} needs the FID Inception weights')
+    if args.inception_score:
+        if args.is_splits < 1:
+            raise SystemExit(f'--is_splits: {args.is_splits}; at least one part expected')
+        args.fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception',
+                                             refusal='--inception_score needs the FID Inception weights')
     if args.rprecision:
         args.damsm_image_encoder = resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder',
                                                    refusal='--rprecision needs the DAMSM image encoder weights')
@@ -191,6 +209,8 @@ _SCORES = {     # metric of MetricSuite.results(): (the flag that asked for it, 
     'FID': ('--fid_against', 'FID: {FID}', 'fid'),
     'PRDC': ('--prdc_against', 'precision: {precision} recall: {recall} density: {density} coverage: {coverage} (k={k}, n={n_real}/{n_fake})', 'prdc'),
     'R-precision': ('--rprecision', 'R-precision: {r_precision} +- {std} (k={k}, n={n})', 'r_precision'),
+    'KID': ('--kid_against', 'KID: {kid} +- {std} (subsets={subsets}, size={subset_size}, n={n_real}/{n_fake})', 'kid'),
+    'IS': ('--inception_score', 'IS: {inception_score} +- {std} (splits={splits}, n={n})', 'inception_score'),
 }
 
 
@@ -248,12 +268,17 @@ def main(argv=None):
         except (ImportError, ValueError) as e:
             raise SystemExit(f'--damsm_image_encoder: {e}')
     # the sampled images are scored from the device, as the bytes of the PNGs (xmc_gan_amd/evaluate.py: one pass serves every metric asked for)
-    suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against) else '', args.prdc_k if args.prdc_against else 0,
+    more = {}                                                        # (KID and the Inception Score: no argument at all while both are off)
+    if args.kid_against:
+        more.update(kid=True, kid_subsets=args.kid_subsets, kid_subset_size=args.kid_subset_size, kid_seed=args.seed)
+    if args.inception_score:
+        more.update(inception_score=args.is_splits)
+    suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against or more) else '', args.prdc_k if args.prdc_against else 0,
                         args.damsm_image_encoder if args.rprecision else '', text_encoder, args.rp_k, args.rp_splits, args.seed,
-                        fid=bool(args.fid_against))
+                        fid=bool(args.fid_against), **more)
     for metric, why in suite.why.items():
         raise SystemExit(f'{_SCORES[metric][0]}: {why}')
-    suite.real_from_path(args.fid_against, args.prdc_against, bs)
+    suite.real_from_path(args.fid_against, args.prdc_against, bs, **({'kid_path': args.kid_against} if args.kid_against else {}))
     cap_step = max(1, bs // M)                                       # captions per batch: about `bs` forwards' worth of images
     try:
         for c0 in range(0, n, cap_step):
@@ -314,7 +339,7 @@ def main(argv=None):
                     cfg=os.path.abspath(args.cfg), config_name=cfg.CONFIG_NAME, generator=cfg.GEN.ENCODER_NAME, img_size=S,
                     seed=args.seed, precision=ops.precision(), truncation=args.truncation, n_per_caption=K, best_of=args.best_of or None,
                     captions=n, fid=scores.pop('fid', {}).get('FID'), grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
-    manifest.update({key: scores[key] for key in ('r_precision', 'prdc') if key in scores})     # (only when asked for, in the order of before)
+    manifest.update({key: scores[key] for key in ('r_precision', 'prdc', 'kid', 'inception_score') if key in scores})     # (only when asked for, in the order of before)
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

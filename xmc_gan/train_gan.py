@@ -88,6 +88,15 @@ def parse_args(argv=None):
     parser.add_argument('--prdc', type=int, default=0, metavar='K',
                         help='> 0: eval() also reports improved precision / recall and density / coverage with K nearest neighbours (typical: '
                              '5), from the Inception features it extracts for FID (needs --fid_inception or XMC_FID_INCEPTION).  0 (default): off')
+    parser.add_argument('--kid', action='store_true',
+                        help='eval() also reports the Kernel Inception Distance (mean +- spread over subsets) from the same Inception '
+                             'features (needs --fid_inception or XMC_FID_INCEPTION)')
+    parser.add_argument('--kid_subsets', type=int, default=100, metavar='S', help='--kid: the number of subsets (default 100)')
+    parser.add_argument('--kid_subset_size', type=int, default=1000, metavar='M',
+                        help='--kid: rows per side of a subset (default 1000; at most the number of images scored)')
+    parser.add_argument('--inception_score', type=int, nargs='?', const=10, default=0, metavar='SPLITS',
+                        help='eval() also reports the Inception Score of the generated images over SPLITS consecutive parts (default 10 when '
+                             'the flag is given without a value; needs --fid_inception or XMC_FID_INCEPTION).  0: off')
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
                         help="DAMSM image encoder weights (image_encoder100.pth of AttnGAN's DAMSM archive): eval() also reports R-precision "
                              "(RNN presets; default: $XMC_DAMSM_IMAGE_ENCODER; without either, no R-precision)")
@@ -784,7 +793,8 @@ def _detached(last):
 
 
 # what `eval` scores after an epoch (not part of the reference cfg; main() fills one from --fid_inception, --prdc and --damsm_image_encoder)
-EvalOptions = collections.namedtuple('EvalOptions', 'fid_inception prdc_k damsm_image_encoder', defaults=('', 0, ''))
+EvalOptions = collections.namedtuple('EvalOptions', 'fid_inception prdc_k damsm_image_encoder kid kid_subsets kid_subset_size inception_score',
+                                     defaults=('', 0, '', False, 100, 1000, 0))
 
 
 _EVAL_REPORT = {    # metric of MetricSuite.results(): (its log line, the values that are scalars of that name, the line that says why there is none)
@@ -793,19 +803,44 @@ _EVAL_REPORT = {    # metric of MetricSuite.results(): (its log line, the values
              ('precision', 'recall', 'density', 'coverage'), ' epoch {epoch}, precision / recall / density / coverage not computed: {why}'),
     'R-precision': (' epoch {epoch}, R-precision : {r_precision} +- {std} (k={k}, n={n})', ('r_precision',),
                     ' epoch {epoch}, R-precision not computed: {why}'),
+    'KID': (' epoch {epoch}, KID : {kid} +- {std} (subsets={subsets}, size={subset_size}, n={n_real}/{n_fake})', ('kid',),
+            ' epoch {epoch}, KID not computed: {why}'),
+    'IS': (' epoch {epoch}, IS : {inception_score} +- {std} (splits={splits}, n={n})', ('inception_score',),
+           ' epoch {epoch}, IS not computed: {why}'),
 }
+_EVAL_SCALAR = {'r_precision': 'R_precision', 'kid': 'KID', 'inception_score': 'IS'}     # a value's name -> its scalar's
+_EVAL_METRICS_KEY = {('PRDC', 'k'): 'prdc_k', ('KID', 'std'): 'kid_std', ('KID', 'subsets'): 'kid_subsets', ('KID', 'subset_size'): 'kid_subset_size',
+                     ('KID', 'n_real'): 'kid_n_real', ('KID', 'n_fake'): 'kid_n_fake',
+                     ('IS', 'std'): 'inception_score_std', ('IS', 'splits'): 'inception_score_splits', ('IS', 'n'): 'inception_score_n'}
+
+
+def _new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score):
+    """the keyword arguments of `MetricSuite` for KID and the Inception Score: none at all while both are off"""
+    kid = given.kid if kid is None else kid
+    splits = given.inception_score if inception_score is None else inception_score
+    kw = {}
+    if kid:
+        kw.update(kid=True, kid_subsets=given.kid_subsets if kid_subsets is None else kid_subsets,
+                  kid_subset_size=given.kid_subset_size if kid_subset_size is None else kid_subset_size)
+    if splits:
+        kw.update(inception_score=int(splits))
+    return kw
 
 
 @torch.no_grad()
 def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
-         damsm_image_encoder=None, metrics=None, prdc=None, eval_opts=None):
+         damsm_image_encoder=None, metrics=None, prdc=None, eval_opts=None, kid=None, kid_subsets=None, kid_subset_size=None,
+         inception_score=None):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to ``save_dir/<key>.png`` and,
     unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``, as 8-bit PNGs of (x + 1) * 127.5.  The
     scores are a `MetricSuite`'s (xmc_gan_amd/evaluate.py): FID with ``fid_inception`` (without it: between the two directories, when
     ``pytorch_fid`` imports), precision / recall / density / coverage with ``prdc`` = K > 0 beside it, R-precision with ``damsm_image_encoder``
-    and an ``RNN_ENCODER``; each is the keyword, else ``eval_opts``, else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER.  With ``org_dir`` the real
-    side is cached beside it.  Every score is logged (or one line says why there is none), written to ``writer`` and, FID apart, put into
-    ``metrics`` when a dict is passed ('k' of PRDC as 'prdc_k').  Returns (uint8 tensor of the generated images, FID or None)."""
+    and an ``RNN_ENCODER``, the Kernel Inception Distance with ``kid`` (over ``kid_subsets`` subsets of ``kid_subset_size`` rows) and the
+    Inception Score with ``inception_score`` = SPLITS > 0, both from the same Inception features; each is the keyword, else ``eval_opts``,
+    else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER.  With ``org_dir`` the real side is cached beside it.  Every score is logged (or one
+    line says why there is none), written to ``writer`` and, FID apart, put into ``metrics`` when a dict is passed ('k' of PRDC as 'prdc_k';
+    of KID and IS every name but 'kid' / 'inception_score' carries that word as a prefix: 'kid_std', 'kid_n_real', 'inception_score_n', ...).  Returns (uint8 tensor of the generated images,
+    FID or None)."""
     from PIL import Image
     netG.eval()
     device = next(netG.parameters()).device
@@ -818,7 +853,8 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     given = eval_opts or EvalOptions()
     suite = MetricSuite(device, fid_inception or given.fid_inception or os.environ.get('XMC_FID_INCEPTION', ''),
                         given.prdc_k if prdc is None else prdc,
-                        damsm_image_encoder or given.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', ''), text_encoder)
+                        damsm_image_encoder or given.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', ''), text_encoder,
+                        **_new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score))
     if org_dir:
         suite.open_cache(os.path.dirname(os.path.abspath(org_dir)))
     cnt, outs = 0, []
@@ -852,11 +888,11 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         logger.info(line.format(epoch=state_epoch, **values))
         for key in tags:
             if writer is not None:
-                writer.add_scalar('R_precision' if key == 'r_precision' else key, values[key], state_epoch)
+                writer.add_scalar(_EVAL_SCALAR.get(key, key), values[key], state_epoch)
         if metric == 'FID':
             fid = values['FID']
         elif metrics is not None:
-            metrics.update({('prdc_k' if (metric, k) == ('PRDC', 'k') else k): v for k, v in values.items()})
+            metrics.update({_EVAL_METRICS_KEY.get((metric, k), k): v for k, v in values.items()})
     return (torch.cat(outs) if outs else None), fid
 
 
@@ -969,8 +1005,13 @@ def _checked_args(argv):
     fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception', must_exist=False)
     if not 0 <= args.prdc <= 16:
         raise SystemExit('--prdc K: 0 (off) or 1 <= K <= 16 nearest neighbours')
+    if args.kid_subsets < 1 or args.kid_subset_size < 2:
+        raise SystemExit('--kid_subsets S >= 1 and --kid_subset_size M >= 2')
+    if args.inception_score < 0:
+        raise SystemExit('--inception_score SPLITS: 0 (off) or a positive number of parts')
     eval_opts = EvalOptions(fid_inception, args.prdc,
-                            resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False))
+                            resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False),
+                            args.kid, args.kid_subsets, args.kid_subset_size, args.inception_score)
     return args, aug_policy, eval_opts
 
 
