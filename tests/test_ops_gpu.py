@@ -69,7 +69,7 @@ CONV_CASES = [
     (32, 32, 3, 1, 1, 32, 3),
     (64, 64, 3, 1, 1, 64, 1),      # row-reuse form (round 4): 3 (Cin block, kw) groups per wave, 2 Cout groups
     (32, 64, 3, 1, 1, 32, 2),      # ... 4 Cout groups x 2 group slices
-    (64, 64, 3, 1, 1, 40, 2),      # H = 40: five tile rows (top / inner / bottom borders), W = 40 declines (not a multiple of 32)
+    (64, 64, 3, 1, 1, 40, 2),      # W = 40 is not a multiple of 32: the tile kernel declines, the split-K kernel's 64x64 form takes it
     (64, 32, 1, 1, 0, 32, 2),
     # streaming kernel for 8-channel sources (conv_thin.hip): conv_img forward / conv_out dgrad on maps with H % 8 == 0, W % 32 == 0
     (3, 64, 3, 1, 1, 64, 1),       # 64 output channels, several tiles per image
@@ -84,10 +84,12 @@ CONV_CASES = [
     (64, 512, 1, 1, 0, 32, 67),    # 1x1, two column tiles, M = 68608
     (512, 256, 4, 2, 1, 16, 8),    # small forward; its dgrad (512 -> ... no: 256-ch dy, 512-ch dx) stays on 128-wide tiles
     (256, 512, 4, 2, 1, 32, 258),  # dgrad: dy 512 ch -> dx 256 ch in 4 parity classes of 66048 pixels each on the 256x256 tile
-    # weight gradient by kernel rows (conv_wgrad_row.hip): Cin, Cout % 128 == 0, W a power of two >= 16
-    (128, 128, 3, 1, 1, 32, 2),    # two 32-pixel row segments per K step
-    (128, 256, 3, 1, 1, 64, 1),    # one 64-pixel segment = one image row
-    (256, 128, 3, 1, 1, 128, 1),   # image rows longer than a K step (segments start inside a row)
+    # wide 3x3 layers on maps with W % 32 == 0, H % 8 == 0: the row-reuse tile kernel (conv_wgrad_tile.hip, 64-channel blocks over
+    # grid.y / grid.z) is tried first and takes them; what the row kernel gets on such widths is in tests/test_wgrad_gpu.py
+    (128, 128, 3, 1, 1, 32, 2),    # 2 x 2 channel blocks
+    (128, 256, 3, 1, 1, 64, 1),    # 2 x 4 channel blocks
+    (256, 128, 3, 1, 1, 128, 1),   # 4 x 2 channel blocks, four tile columns
+    # weight gradient by kernel rows (conv_wgrad_row.hip): Cin % 128 == 0 (or 64), Cout % 128 == 0, W a power of two >= 4
     (128, 128, 4, 2, 1, 32, 3),    # 4x4 stride 2: output rows of 16 pixels, 4 segments per step
     (128, 256, 4, 2, 1, 64, 2),    # output rows of 32
     (128, 128, 4, 2, 1, 128, 1),   # output rows of 64: 130 source pixels per segment
