@@ -53,6 +53,7 @@ extern "C" {
  *     xmc_resize_bilinear_f32 and xmc_pool3x3's mode XMC_POOL_AVG_PAD (csrc/fid.hip), xmc_rprecision (csrc/retrieval.hip);
  *     xmc_crop_flip_normalize (csrc/datafeed.hip);
  *     xmc_gtail_bwd (csrc/conv_thin.hip: the generator tail's backward in one pass);
+ *     xmc_gentry_fwd / xmc_gentry_bwd (csrc/conv_thin.hip: a generator block's affine pair and learned 1x1 shortcut in one pass each);
  *     xmc_caption_gather (csrc/captionfeed.hip);
  *     xmc_manifold_slices / xmc_row_sqnorm / xmc_knn_radius2 / xmc_manifold_count (csrc/manifold.hip);
  *     xmc_poly_mmd_tiles / xmc_poly_mmd_sums / xmc_inception_score_ws_bytes / xmc_inception_score (csrc/kid.hip). */
@@ -289,6 +290,22 @@ int xmc_conv_wgrad_bits(const XmcConvDesc* d, float* dwp, void* stream);
  * descriptor with bias / act / res / ...; XMC_DEBUG_DISPATCH=no_gtail_fused): the caller then runs xmc_tanh_bwd, xmc_conv_wgrad_bias
  * and xmc_conv_igemm. */
 int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, float* dbias, int dw_rows, int grid_cap, void* stream);
+/* The entry of a generator block with a learned shortcut (G_Block with in_dim != out_dim), one pass over the block input x [N,H,W,Cin] per
+ * direction.  g0, b0, g1, b1: the affine pair's per-sample vectors, f32 [N,Cin].
+ * xmc_gentry_fwd: h = lrelu(lrelu(x g0 + b0) g1 + b1) (xmc_affine2_act_fwd's bits) and sc = conv1x1(x, wpk) + bias [N,H,W,Cout] (the
+ * streaming 1x1 kernels' bits) from one load of x.  wpk: the forward pack [1][wrows = Cout][Cin]; bias f32 [Cout] or NULL.
+ * xmc_gentry_bwd: dskip = conv1x1^T(dsc) is formed per 16-pixel group, rounded to the storage format and never written; then everything
+ * xmc_affine2_act_bwd_dot_pool does with dx_in = dskip: dx (bit for bit), the four sums dg0 / db0 / dg1 / db1 (f32 [N,Cin], ACCUMULATED:
+ * zeroed by the caller; another order of additions than the affine kernel's) and, with dx_pool != NULL, the 2x2 sum pool of the rounded
+ * dx [N,H/2,W/2,Cin].  wpk_t: the data-gradient pack [1][wrows = Cin][Cout].  The fixed-order mode does not apply (as for the affine
+ * backward).  grid_cap > 0 limits the persistent grid (tests).  Both return 1 and launch nothing for what they do not take: f32 storage,
+ * (Cin, Cout) other than (64, 32), (128, 64), (256, 128), padded weight rows, odd H or W with dx_pool, XMC_DEBUG_DISPATCH=no_gentry_fused:
+ * the caller then runs the affine and 1x1 launches separately. */
+int xmc_gentry_fwd(const void* x, const float* g0, const float* b0, const float* g1, const float* b1, const void* wpk, const float* bias,
+                   void* h, void* sc, int N, int H, int W, int Cin, int Cout, int wrows, float slope, int dtype, int grid_cap, void* stream);
+int xmc_gentry_bwd(const void* x, const void* dy, const void* dsc, const float* g0, const float* b0, const float* g1, const float* b1,
+                   const void* wpk_t, void* dx, void* dx_pool, float* dg0, float* db0, float* dg1, float* db1, int N, int H, int W,
+                   int Cin, int Cout, int wrows, float slope, int dtype, int grid_cap, void* stream);
 int xmc_tanh_bwd(const void* dy, const void* y, void* dx, int64_t n, int dtype, void* stream);
 /* y = a + (*alpha_dev) * b                  (shortcut + gamma*residual, df_gan.py:200,284) */
 int xmc_axpby(const void* a, const void* b, const float* alpha_dev, void* y, int64_t n, int dtype, void* stream);

@@ -90,6 +90,44 @@ __device__ __forceinline__ float lrelu_slope(float ref) { return ref > 0.f ? 1.f
 // dx = dy * tanh'(x) from y = tanh(x): ONE spelling for xmc_tanh_bwd and for the kernel that applies it while it stages dy
 // (conv_thin.hip, gtail_bwd_kernel), pinned (xmc_pin_f32) so that both round the same f32 value to 16 bits
 __device__ __forceinline__ float tanh_bwd_f(float dy, float y) { return xmc_pin_f32(dy * (1.f - y * y)); }
+// The DF-GAN affine pair lrelu(lrelu(x g0 + b0) g1 + b1) on one element (`two` false: the single modulation lrelu(x g0 + b0)): ONE
+// spelling for affine2_fwd_kernel (pointwise.hip) and for the generator block entry (conv_thin.hip, gentry_fwd_kernel), which promises
+// its bits.  Both sums are fused multiply-adds by name, and the result is pinned: always an f32 value, then one conversion to 16 bits.
+__device__ __forceinline__ float affine2_fwd_f(float x, float g0, float b0, float g1, float b1, float slope, bool two) {
+    float u = __builtin_fmaf(x, g0, b0);
+    u = u > 0.f ? u : slope * u;
+    const float t = __builtin_fmaf(u, g1, b1);
+    return xmc_pin_f32(two ? (t > 0.f ? t : slope * t) : u);
+}
+// ... and its backward on one 8-channel unit of one pixel, shared by affine2_bwd_kernel and gentry_bwd_kernel: xv (x on entry) leaves as
+// dx BEFORE its rounding = dy * d(pair)/dx [+ o, another gradient of x, when has_in]; the four per-sample sums take their terms.  al:
+// dy's scale; dacc (optional): += <dy, y> with y the pair's ROUNDED output (see affine2_bwd_kernel).  The product du * g0 is pinned, so
+// that the sum with `o` is an addition of two rounded f32 values wherever this is inlined.
+template <int DT>
+__device__ __forceinline__ void affine2_bwd_unit(float (&xv)[8], const float (&dv)[8], const float (&o)[8], bool has_in, bool two, float slope,
+                                                 float al, float* dacc, const float (&G0)[8], const float (&B0)[8], const float (&G1)[8],
+                                                 const float (&B1)[8], float (&sg0)[8], float (&sb0)[8], float (&sg1)[8], float (&sb1)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float u = __builtin_fmaf(xv[k], G0[k], B0[k]);
+        const float a1 = u > 0.f ? u : slope * u;
+        const float v = __builtin_fmaf(a1, G1[k], B1[k]);
+        if (dacc) {
+            const float y2 = two ? (v > 0.f ? v : slope * v) : a1;
+            *dacc += dv[k] * (DT == XMC_BF16 ? (float)(xmc_h16)y2 : y2);       // the consumer read the stored (rounded) y
+        }
+        const float dvk = dv[k] * al;
+        const float dvv = two ? dvk * (v > 0.f ? 1.f : slope) : dvk;
+        sg1[k] += dvv * a1; sb1[k] += dvv;
+        const float du = dvv * G1[k] * (u > 0.f ? 1.f : slope);
+        sg0[k] += du * xv[k]; sb0[k] += du;
+        xv[k] = xmc_pin_f32(du * G0[k]);
+    }
+    if (has_in) {                 // another gradient of x (the block's shortcut branch) joins here instead of in an add pass
+#pragma unroll
+        for (int k = 0; k < 8; ++k) xv[k] += o[k];
+    }
+}
 // one 16-byte unit (8 channels) x LeakyReLU' from its sign byte (bit k set: channel k positive), rounded back to the 16-bit format:
 // what xmc_signmask_apply stores, computed where the unit is staged (XmcConvDesc.mask_bits)
 __device__ __forceinline__ u32x4 xmc_apply_sign_bits(u32x4 v, unsigned b) {

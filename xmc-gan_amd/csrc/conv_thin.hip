@@ -635,6 +635,385 @@ int launch_pww(const XmcConvDesc& d, int ngroups, hipStream_t st, const unsigned
     return 0;
 }
 
+// ---- The entry of a generator block with a learned shortcut (G_Block with in_dim != out_dim, df_gan.py:199-216; ops.GBlockEntryFn,
+// DESIGN 4.1): the block input x feeds the affine pair h = lrelu(lrelu(x g0 + b0) g1 + b1) AND the 1x1 shortcut sc = c_sc(x), and in the
+// backward both gradients of x meet again.  Two kernels, one per direction, stream x ONCE each:
+//   * gentry_fwd_kernel is pw1x1_kernel / pw1x1w_kernel (same MFMA, same channel-to-K mapping, same order of K steps, same epilogue: sc
+//     is theirs bit for bit) whose 16-byte units, on their way into the B operand, also pass through affine2_fwd_f and leave as h;
+//   * gentry_bwd_kernel forms dskip = c_sc^T dsc per 16-pixel group on the MFMAs (again the 1x1 kernels' arithmetic), rounds it to the
+//     storage format -- the value affine2_bwd_kernel reads from memory today -- and hands it through a wave-private LDS slab to the
+//     affine backward's own thread-to-unit mapping (a lane owns ONE 8-channel unit of many pixels: 32 parameter and 32 sum registers),
+//     which runs affine2_bwd_unit on it: dx, its 2x2 sum pool and the four per-sample sums.  dskip is never written.
+// Work: an image is cut into groups of 16 pixels (POOL: four 2x2 quads, so that both rows of a quad are one lane's two steps and its
+// two columns are lanes C8 apart); a group never straddles images, a partial last group is masked.  A workgroup owns a contiguous run of
+// groups, its waves take them in turn, and each wave keeps its image's parameters (forward: LDS, read per unit; backward: registers)
+// and flushes its sums with one set of atomics per image it met.  The grid is the resident set (see gtail_bwd_kernel's note).
+struct GEntryArgs {
+    const void *x, *dy, *dsc, *wpk;
+    void *h, *sc, *dx, *dx_pool;
+    const float *bias, *g0, *b0, *g1, *b1;
+    float *dg0, *db0, *dg1, *db1;
+    int N, H, W, gpi, nvg, per;          // groups per image, N * gpi, groups per workgroup
+    float slope;
+};
+
+// weight rows -> LDS as pw1x1w_kernel stages its slice (rows padded by 16 bytes; physical row (block j, r) <- logical channel
+// (j/2)*32 + (r/4)*8 + (j%2)*4 + r%4), or -> registers as pw1x1_kernel holds them
+template <int KS, int TN, bool WLDS, int NW>
+__device__ __forceinline__ void gentry_weights(const u32x4* __restrict__ w16, unsigned char* wlds, u32x4 (&wf)[WLDS ? 1 : KS][WLDS ? 1 : TN], int tid, int fr, int fc) {
+    constexpr int RSTR = KS * 64 + 16;
+    if constexpr (WLDS) {
+        for (int id = tid; id < TN * 16 * KS * 4; id += NW * 64) {
+            const int row = id / (KS * 4), ch = id - row * (KS * 4);
+            const int j = row >> 4, r = row & 15;
+            const int lrow = (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
+            *reinterpret_cast<u32x4*>(wlds + row * RSTR + ch * 16) = w16[(size_t)lrow * (KS * 4) + ch];
+        }
+        __syncthreads();
+    } else {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int lrow = (j >> 1) * 32 + (fr >> 2) * 8 + (j & 1) * 4 + (fr & 3);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) wf[ks][j] = w16[(size_t)lrow * (KS * 4) + ks * 4 + fc];
+        }
+    }
+}
+
+template <int KS, int TN, bool WLDS, int NW>      // KS = Cin / 32 K-steps, TN = Cout / 16 row blocks, NW waves per workgroup
+__global__ __launch_bounds__(NW * 64) void gentry_fwd_kernel(const GEntryArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char glds[];
+    constexpr int CIN = KS * 32, C8 = KS * 4, CO8 = TN * 2, UNR = 4;
+    constexpr int RSTR = KS * 64 + 16, WBYTES = WLDS ? TN * 16 * RSTR : 0;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fr = lane & 15, fc = lane >> 4;
+    const u32x4* __restrict__ src16 = reinterpret_cast<const u32x4*>(a.x);
+    bf16x8* __restrict__ h8 = reinterpret_cast<bf16x8*>(a.h);
+    bf16x8* __restrict__ sc8 = reinterpret_cast<bf16x8*>(a.sc);
+    float* const par = reinterpret_cast<float*>(glds + WBYTES) + wv * 4 * CIN;          // this wave's image: [g0 | b0 | g1 | b1][CIN]
+    u32x4 wf[WLDS ? 1 : KS][WLDS ? 1 : TN];
+    gentry_weights<KS, TN, WLDS, NW>(reinterpret_cast<const u32x4*>(a.wpk), glds, wf, tid, fr, fc);
+    float bias8[WLDS ? 1 : TN / 2][8];
+    if constexpr (!WLDS) {
+#pragma unroll
+        for (int u = 0; u < TN / 2; ++u)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) bias8[u][c] = a.bias ? a.bias[u * 32 + fc * 8 + c] : 0.f;
+    }
+    const float slope = a.slope, one = 1.f;          // `one`: the 1x1 kernels' epilogue fmaxf(v, v * slope) with no activation
+    const int HW = a.H * a.W;
+    const int lo = blockIdx.x * a.per, hi = min(lo + a.per, a.nvg);
+    int cur = -1;
+    for (int g0 = lo + wv * UNR; g0 < hi; g0 += NW * UNR) {
+        const int n = g0 / a.gpi, gl0 = g0 - n * a.gpi;              // gpi and `per` are multiples of UNR: the UNR groups share the image
+        if (n != cur) {
+            const float* vec[4] = {a.g0, a.b0, a.g1, a.b1};
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                for (int c = lane; c < CIN; c += 64) par[q * CIN + c] = vec[q][(size_t)n * CIN + c];
+            __builtin_amdgcn_wave_barrier();
+            cur = n;
+        }
+        size_t pix[UNR];
+        bool ok[UNR];
+        u32x4 pf[UNR][KS];
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int p = (gl0 + r) * 16 + fr;
+            ok[r] = p < HW;
+            pix[r] = (size_t)n * HW + (ok[r] ? p : HW - 1);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) pf[r][ks] = src16[pix[r] * C8 + ks * 4 + fc];
+        }
+        // h: the affine pair on every unit this lane holds
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const f32x4* pq = reinterpret_cast<const f32x4*>(par + (ks * 4 + fc) * 8);
+            float P[4][8];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 lo4 = pq[q * (CIN / 4)], hi4 = pq[q * (CIN / 4) + 1];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { P[q][k] = lo4[k]; P[q][4 + k] = hi4[k]; }
+            }
+#pragma unroll
+            for (int r = 0; r < UNR; ++r) {
+                const bf16x8 xv = __builtin_bit_cast(bf16x8, pf[r][ks]);
+                bf16x8 o;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) o[k] = (xmc_h16)affine2_fwd_f((float)xv[k], P[0][k], P[1][k], P[2][k], P[3][k], slope, true);
+                if (ok[r]) h8[pix[r] * C8 + ks * 4 + fc] = o;
+            }
+        }
+        // sc: the 1x1 product of the same units
+        if constexpr (!WLDS) {
+#pragma unroll
+            for (int r = 0; r < UNR; ++r) {
+                if ((gl0 + r) * 16 >= HW) break;
+                f32x4 acc[TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[j] = XMC_MFMA_16x16x32(__builtin_bit_cast(bf16x8, wf[ks][j]), __builtin_bit_cast(bf16x8, pf[r][ks]), acc[j], 0, 0, 0);
+#pragma unroll
+                for (int u = 0; u < TN / 2; ++u) {
+                    bf16x8 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float x0 = acc[2 * u][q] + bias8[u][q], x1 = acc[2 * u + 1][q] + bias8[u][4 + q];
+                        o[q] = (xmc_h16)fmaxf(x0, x0 * one);
+                        o[4 + q] = (xmc_h16)fmaxf(x1, x1 * one);
+                    }
+                    if (ok[r]) sc8[pix[r] * CO8 + u * 4 + fc] = o;
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int u = 0; u < TN / 2; ++u) {
+                f32x4 acc[UNR][2];
+#pragma unroll
+                for (int r = 0; r < UNR; ++r) acc[r][0] = acc[r][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                const unsigned char* const wr = glds + (u * 32 + fr) * RSTR + fc * 16;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const bf16x8 wa = *reinterpret_cast<const bf16x8*>(wr + ks * 64), wb = *reinterpret_cast<const bf16x8*>(wr + 16 * RSTR + ks * 64);
+#pragma unroll
+                    for (int r = 0; r < UNR; ++r) {
+                        acc[r][0] = XMC_MFMA_16x16x32(wa, __builtin_bit_cast(bf16x8, pf[r][ks]), acc[r][0], 0, 0, 0);
+                        acc[r][1] = XMC_MFMA_16x16x32(wb, __builtin_bit_cast(bf16x8, pf[r][ks]), acc[r][1], 0, 0, 0);
+                    }
+                }
+                float b8[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) b8[c] = a.bias ? a.bias[u * 32 + fc * 8 + c] : 0.f;
+#pragma unroll
+                for (int r = 0; r < UNR; ++r) {
+                    bf16x8 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float x0 = acc[r][0][q] + b8[q], x1 = acc[r][1][q] + b8[4 + q];
+                        o[q] = (xmc_h16)fmaxf(x0, x0 * one);
+                        o[4 + q] = (xmc_h16)fmaxf(x1, x1 * one);
+                    }
+                    if (ok[r]) sc8[pix[r] * CO8 + u * 4 + fc] = o;
+                }
+            }
+        }
+    }
+}
+
+template <int KS, int TN, bool WLDS, bool POOL, int NW>      // KS = Cout / 32 K-steps of the data gradient, TN = Cin / 16 row blocks
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gentry_bwd_kernel(const GEntryArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char glds[];
+    constexpr int C8 = TN * 2, CS8 = KS * 4, PPS = 64 / C8, NPAIR = C8 / 8;        // PPS pixels per wave step, NPAIR pairs of steps per group
+    constexpr int RSTR = KS * 64 + 16, WBYTES = WLDS ? TN * 16 * RSTR : 0, SSTR = C8 * 16 + 16;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fr = lane & 15, fc = lane >> 4;
+    const int cc = lane % C8, pg = lane / C8;                    // the affine backward's roles: unit cc of pixel lane pg
+    const u32x4* __restrict__ x16 = reinterpret_cast<const u32x4*>(a.x);
+    const u32x4* __restrict__ dy16 = reinterpret_cast<const u32x4*>(a.dy);
+    const u32x4* __restrict__ dsc16 = reinterpret_cast<const u32x4*>(a.dsc);
+    unsigned char* const slab = glds + WBYTES + wv * 16 * SSTR;  // this wave's dskip: [16 slots][C8 units], rows padded by 16 bytes
+    u32x4 wf[WLDS ? 1 : KS][WLDS ? 1 : TN];
+    gentry_weights<KS, TN, WLDS, NW>(reinterpret_cast<const u32x4*>(a.wpk), glds, wf, tid, fr, fc);
+    const float slope = a.slope;
+    const int HW = a.H * a.W, Wq = a.W >> 1;
+    const int nunits = POOL ? (a.H >> 1) * Wq : HW;              // quads or pixels of an image
+    // slot f of group gl -> pixel of the image, or -1.  POOL: slot = (step s, pixel lane) with s & 1 the quad's row and the lane's low bit
+    // its column; else 16 consecutive pixels
+    auto slot_pixel = [&](int gl, int f) -> int {
+        if constexpr (POOL) {
+            const int s = f / PPS, pl = f % PPS;
+            const int q = gl * 4 + (s >> 1) * (PPS / 2) + (pl >> 1);
+            if (q >= nunits) return -1;
+            const int qy = q / Wq, qx = q - qy * Wq;
+            return (2 * qy + (s & 1)) * a.W + 2 * qx + (pl & 1);
+        } else {
+            const int p = gl * 16 + f;
+            return p < nunits ? p : -1;
+        }
+    };
+    float G0[8], B0[8], G1[8], B1[8], sg0[8], sb0[8], sg1[8], sb1[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sg0[k] = sb0[k] = sg1[k] = sb1[k] = 0.f;
+    // the sums of image n: over the pixel lanes of the wave, then one set of atomics (the accumulators arrive zero)
+    auto flush = [&](int n) {
+        float* const outs[4] = {a.dg0, a.db0, a.dg1, a.db1};
+        float* const sums[4] = {sg0, sb0, sg1, sb1};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                float v = sums[q][k];
+#pragma unroll
+                for (int o = C8; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+                if (lane < C8) atomicAdd(&outs[q][((size_t)n * C8 + cc) * 8 + k], v);
+                sums[q][k] = 0.f;
+            }
+    };
+    auto load_dsc = [&](int g, u32x4 (&pf)[KS]) {
+        const int n = g / a.gpi, p = slot_pixel(g - n * a.gpi, fr);
+        const size_t idx = ((size_t)n * HW + (p < 0 ? 0 : p)) * CS8;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) pf[ks] = dsc16[idx + ks * 4 + fc];
+    };
+    // the affine backward's operands of step pair t of group g (a masked slot reads pixel 0 of the image and drops its results)
+    struct PairOps { int px[2]; u32x4 xq[2], dq[2]; };
+    auto load_pair = [&](int g, int t, PairOps& o) {
+        const int n = g / a.gpi, gl = g - n * a.gpi;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            o.px[e] = slot_pixel(gl, (2 * t + e) * PPS + pg);
+            const size_t idx = ((size_t)n * HW + (o.px[e] < 0 ? 0 : o.px[e])) * C8 + cc;
+            o.xq[e] = x16[idx];
+            o.dq[e] = dy16[idx];
+        }
+    };
+    const int lo = blockIdx.x * a.per, hi = min(lo + a.per, a.nvg);
+    int g = lo + wv, cur = -1;
+    u32x4 pfs[KS];
+    PairOps cu;
+    constexpr bool PRE = KS < 4;          // the next group's dsc units in flight (KS = 4: their 16 registers are the ones that would spill)
+    if (g < hi) { load_dsc(g, pfs); load_pair(g, 0, cu); }
+    for (; g < hi; g += NW) {
+        const int n = g / a.gpi, gl = g - n * a.gpi;
+        if (n != cur) {
+            if (cur >= 0) flush(cur);
+            const size_t pb = ((size_t)n * C8 + cc) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { G0[k] = a.g0[pb + k]; B0[k] = a.b0[pb + k]; G1[k] = a.g1[pb + k]; B1[k] = a.b1[pb + k]; }
+            cur = n;
+        }
+        u32x4 pfn[KS];
+        if (PRE && g + NW < hi) load_dsc(g + NW, pfn);
+        else {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) pfn[ks] = pfs[ks];
+        }
+        // dskip of the group's 16 slots: the 1x1 data gradient's MFMAs and epilogue (no bias, no activation: acc + 0 as there), rounded
+#pragma unroll
+        for (int u = 0; u < TN / 2; ++u) {
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                bf16x8 wa, wb;
+                if constexpr (WLDS) {
+                    const unsigned char* const wr = glds + (u * 32 + fr) * RSTR + fc * 16 + ks * 64;
+                    wa = *reinterpret_cast<const bf16x8*>(wr);
+                    wb = *reinterpret_cast<const bf16x8*>(wr + 16 * RSTR);
+                } else {
+                    wa = __builtin_bit_cast(bf16x8, wf[ks][2 * u]);
+                    wb = __builtin_bit_cast(bf16x8, wf[ks][2 * u + 1]);
+                }
+                acc0 = XMC_MFMA_16x16x32(wa, __builtin_bit_cast(bf16x8, pfs[ks]), acc0, 0, 0, 0);
+                acc1 = XMC_MFMA_16x16x32(wb, __builtin_bit_cast(bf16x8, pfs[ks]), acc1, 0, 0, 0);
+            }
+            bf16x8 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                o[q] = (xmc_h16)(acc0[q] + 0.f);
+                o[4 + q] = (xmc_h16)(acc1[q] + 0.f);
+            }
+            *reinterpret_cast<bf16x8*>(slab + fr * SSTR + (u * 4 + fc) * 16) = o;
+        }
+        __builtin_amdgcn_wave_barrier();
+        // the affine backward, one pair of steps at a time, the next pair's operands (or the next group's first) in flight
+#pragma unroll 1
+        for (int t = 0; t < NPAIR; ++t) {
+            const bool more = t + 1 < NPAIR;
+            const int gn = more ? g : g + NW;
+            PairOps nx = cu;
+            if (gn < hi) load_pair(gn, more ? t + 1 : 0, nx);
+            float acc8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const bool live = cu.px[e] >= 0;
+                const bf16x8 xb = __builtin_bit_cast(bf16x8, cu.xq[e]), db = __builtin_bit_cast(bf16x8, cu.dq[e]);
+                const bf16x8 ob = *reinterpret_cast<const bf16x8*>(slab + ((2 * t + e) * PPS + pg) * SSTR + cc * 16);
+                float xv[8], dv[8], ov[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { xv[k] = (float)xb[k]; dv[k] = live ? (float)db[k] : 0.f; ov[k] = live ? (float)ob[k] : 0.f; }
+                affine2_bwd_unit<XMC_BF16>(xv, dv, ov, true, true, slope, 1.f, nullptr, G0, B0, G1, B1, sg0, sb0, sg1, sb1);
+                if (live) Vec8<XMC_BF16>::store(a.dx, ((size_t)n * HW + cu.px[e]) * C8 + cc, xv);
+                if (POOL) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc8[k] += (float)(xmc_h16)xv[k];
+                }
+                __builtin_amdgcn_sched_barrier(0);          // one pixel after the other: interleaved, their temporaries do not fit
+            }
+            if (POOL) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc8[k] += __shfl_xor(acc8[k], C8, 64);       // the quad's other column: lane ^ C8
+                const int q = gl * 4 + t * (PPS / 2) + (pg >> 1);
+                if ((pg & 1) == 0 && cu.px[0] >= 0) Vec8<XMC_BF16>::store(a.dx_pool, ((size_t)n * nunits + q) * C8 + cc, acc8);
+            }
+            cu = nx;
+        }
+        __builtin_amdgcn_wave_barrier();          // the next group's dskip is written after these reads
+        if (PRE) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) pfs[ks] = pfn[ks];
+        } else if (g + NW < hi) {
+            load_dsc(g + NW, pfs);
+        }
+    }
+    if (cur >= 0) flush(cur);
+}
+
+// workgroups of `kernel` that are resident on the device at once
+template <typename K>
+int gentry_resident(K kernel, int threads, size_t lds) {
+    int dev = 0, cus = 0, nb = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds) != hipSuccess || nb < 1) nb = 1;
+    (void)hipGetLastError();
+    return cus * nb;
+}
+
+// grid (resident set, capped) and the groups per workgroup, a multiple of `unit`
+inline int gentry_grid(GEntryArgs& a, int resident, int grid_cap, int unit) {
+    int gx = resident;
+    if (grid_cap > 0 && gx > grid_cap) gx = grid_cap;
+    const int chunks = (a.nvg + unit - 1) / unit;
+    if (gx > chunks) gx = chunks;
+    a.per = (chunks + gx - 1) / gx * unit;
+    return (a.nvg + a.per - 1) / a.per;
+}
+
+template <int KS, int TN, bool WLDS, int NW>
+int launch_gentry_fwd(GEntryArgs& a, int grid_cap, hipStream_t st) {
+    constexpr size_t lds = (WLDS ? TN * 16 * (KS * 64 + 16) : 0) + NW * 4 * KS * 32 * sizeof(float);
+    auto kernel = gentry_fwd_kernel<KS, TN, WLDS, NW>;
+    if (lds > 64 * 1024) XMC_ALLOW_BIG_LDS((*kernel));
+    static const int resident = gentry_resident(kernel, NW * 64, lds);
+    const int gx = gentry_grid(a, resident, grid_cap, 4);
+    hipLaunchKernelGGL(kernel, dim3(gx), dim3(NW * 64), lds, st, a);
+    xmc_note_kernel("gentry_fwd_kernel<%d, %d>", KS, TN);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int KS, int TN, bool WLDS, int NW>
+int launch_gentry_bwd(GEntryArgs& a, int grid_cap, hipStream_t st) {
+    constexpr size_t lds = (WLDS ? TN * 16 * (KS * 64 + 16) : 0) + NW * 16 * (TN * 2 * 16 + 16);
+    if (a.dx_pool) {
+        auto kernel = gentry_bwd_kernel<KS, TN, WLDS, true, NW>;
+        if (lds > 64 * 1024) XMC_ALLOW_BIG_LDS((*kernel));
+        static const int resident = gentry_resident(kernel, NW * 64, lds);
+        hipLaunchKernelGGL(kernel, dim3(gentry_grid(a, resident, grid_cap, 1)), dim3(NW * 64), lds, st, a);
+    } else {
+        auto kernel = gentry_bwd_kernel<KS, TN, WLDS, false, NW>;
+        if (lds > 64 * 1024) XMC_ALLOW_BIG_LDS((*kernel));
+        static const int resident = gentry_resident(kernel, NW * 64, lds);
+        hipLaunchKernelGGL(kernel, dim3(gentry_grid(a, resident, grid_cap, 1)), dim3(NW * 64), lds, st, a);
+    }
+    xmc_note_kernel("gentry_bwd_kernel<%d, %d, %d>", KS, TN, a.dx_pool ? 1 : 0);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- 8 stored output channels (conv_out of the generator: 32 -> 3, df_gan.py:85-87, + bias + tanh).  On the 32-wide tile
 // kernel this layer multiplies 32 output channels for the 8 it stores and is bound by that waste (0.66 ms where its 1.34 GB
 // of tensors take 0.27 ms).  Here the output channels are the 16 rows of the MFMA (8 used), the B operand is the lane's
@@ -810,6 +1189,55 @@ extern "C" int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, 
     xmc_note_kernel("gtail_bwd_kernel<%d>", dwp ? 1 : 0);
     XMC_LAUNCH_CHECK();
     return 0;
+}
+
+// The entry of a generator block with a learned shortcut, one pass per direction (gentry_fwd_kernel / gentry_bwd_kernel;
+// include/xmc_gan_hip.h).  0 = launched, 1 = not these kernels' case, < 0 = error
+static int gentry_case(int N, int H, int W, int Cin, int Cout, int dtype) {
+    static const bool off = xmc_debug_off("no_gentry_fused");
+    if (off || dtype != XMC_BF16) return 1;
+    if (!((Cin == 64 && Cout == 32) || (Cin == 128 && Cout == 64) || (Cin == 256 && Cout == 128))) return 1;
+    if ((int64_t)N * H * W * (Cin / 8) >= (1ll << 31) || (int64_t)N * ((int64_t)H * W / 16 + 4) >= (1ll << 30)) return 1;
+    return 0;
+}
+
+extern "C" int xmc_gentry_fwd(const void* x, const float* g0, const float* b0, const float* g1, const float* b1, const void* wpk, const float* bias,
+                              void* h, void* sc, int N, int H, int W, int Cin, int Cout, int wrows, float slope, int dtype, int grid_cap, void* stream) {
+    if (!x || !g0 || !b0 || !g1 || !b1 || !wpk || !h || !sc) return XMC_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || Cin < 8 || Cout < 8 || Cin % 8 || Cout % 8) return XMC_ESHAPE;
+    if (const int rc = gentry_case(N, H, W, Cin, Cout, dtype)) return rc;
+    if (wrows != Cout) return 1;                           // the packed weights [Cout][Cin], rows unpadded
+    GEntryArgs a = {};
+    a.x = x; a.wpk = wpk; a.h = h; a.sc = sc; a.bias = bias;
+    a.g0 = g0; a.b0 = b0; a.g1 = g1; a.b1 = b1;
+    a.N = N; a.H = H; a.W = W; a.slope = slope;
+    a.gpi = ((H * W + 15) / 16 + 3) / 4 * 4;               // 16-pixel groups of an image, padded to the four a wave has in flight
+    a.nvg = N * a.gpi;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (Cin == 64) return launch_gentry_fwd<2, 2, false, 4>(a, grid_cap, st);
+    if (Cin == 128) return launch_gentry_fwd<4, 4, true, 4>(a, grid_cap, st);
+    return launch_gentry_fwd<8, 8, true, 8>(a, grid_cap, st);
+}
+
+extern "C" int xmc_gentry_bwd(const void* x, const void* dy, const void* dsc, const float* g0, const float* b0, const float* g1, const float* b1,
+                              const void* wpk_t, void* dx, void* dx_pool, float* dg0, float* db0, float* dg1, float* db1, int N, int H, int W,
+                              int Cin, int Cout, int wrows, float slope, int dtype, int grid_cap, void* stream) {
+    if (!x || !dy || !dsc || !g0 || !b0 || !g1 || !b1 || !wpk_t || !dx || !dg0 || !db0 || !dg1 || !db1) return XMC_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || Cin < 8 || Cout < 8 || Cin % 8 || Cout % 8) return XMC_ESHAPE;
+    if (const int rc = gentry_case(N, H, W, Cin, Cout, dtype)) return rc;
+    if (wrows != Cin) return 1;
+    if (dx_pool && ((H & 1) || (W & 1))) return 1;
+    GEntryArgs a = {};
+    a.x = x; a.dy = dy; a.dsc = dsc; a.wpk = wpk_t; a.dx = dx; a.dx_pool = dx_pool;
+    a.g0 = g0; a.b0 = b0; a.g1 = g1; a.b1 = b1;
+    a.dg0 = dg0; a.db0 = db0; a.dg1 = dg1; a.db1 = db1;
+    a.N = N; a.H = H; a.W = W; a.slope = slope;
+    a.gpi = dx_pool ? ((H / 2) * (W / 2) + 3) / 4 : (H * W + 15) / 16;         // groups of four 2x2 quads, or of 16 pixels
+    a.nvg = N * a.gpi;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (Cin == 64) return launch_gentry_bwd<1, 4, false, 4>(a, grid_cap, st);
+    if (Cin == 128) return launch_gentry_bwd<2, 8, true, 4>(a, grid_cap, st);
+    return launch_gentry_bwd<4, 16, true, 8>(a, grid_cap, st);
 }
 
 // 0 = launched, 1 = not this kernel's case, < 0 = error

@@ -373,12 +373,7 @@ __global__ void affine2_fwd_kernel(const void* x, const float* g0, const float* 
         const size_t idx = ((size_t)n * HW + p) * C8 + cc;
         Vec8<DT>::load(x, idx, v);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float u = v[k] * G0[k] + B0[k];
-            u = u > 0.f ? u : slope * u;
-            const float t = u * G1[k] + B1[k];
-            v[k] = two ? (t > 0.f ? t : slope * t) : u;
-        }
+        for (int k = 0; k < 8; ++k) v[k] = affine2_fwd_f(v[k], G0[k], B0[k], G1[k], B1[k], slope, two);
         Vec8<DT>::store(y, idx, v);
     }
 }
@@ -412,28 +407,9 @@ __global__ __launch_bounds__(NT, 2) void affine2_bwd_kernel(        // two pixel
         G0[k] = g0[pb + k]; B0[k] = b0[pb + k]; G1[k] = two ? g1[pb + k] : 1.f; B1[k] = two ? b1[pb + k] : 0.f;
         sg0[k] = sb0[k] = sg1[k] = sb1[k] = 0.f;
     }
-    // one pixel from its loaded operands: dx is stored and (POOL) added, rounded as stored, to acc8
+    // one pixel from its loaded operands (affine2_bwd_unit, common.h): dx is stored and (POOL) added, rounded as stored, to acc8
     auto pixel = [&](size_t idx, float (&xv)[8], const float (&dv)[8], const float (&o)[8], float* acc8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float u = xv[k] * G0[k] + B0[k];
-            float a1 = u > 0.f ? u : slope * u;
-            float v = a1 * G1[k] + B1[k];
-            if (dot) {
-                const float y2 = two ? (v > 0.f ? v : slope * v) : a1;
-                dacc += dv[k] * (DT == XMC_BF16 ? (float)(xmc_h16)y2 : y2);       // the consumer read the stored (rounded) y
-            }
-            const float dvk = dv[k] * al;
-            float dvv = two ? dvk * (v > 0.f ? 1.f : slope) : dvk;
-            sg1[k] += dvv * a1; sb1[k] += dvv;
-            float du = dvv * G1[k] * (u > 0.f ? 1.f : slope);
-            sg0[k] += du * xv[k]; sb0[k] += du;
-            xv[k] = du * G0[k];
-        }
-        if (dx_in) {                  // another gradient of x (the block's shortcut branch) joins here instead of in an add pass
-#pragma unroll
-            for (int k = 0; k < 8; ++k) xv[k] += o[k];
-        }
+        affine2_bwd_unit<DT>(xv, dv, o, dx_in != nullptr, two, slope, al, dot ? &dacc : nullptr, G0, B0, G1, B1, sg0, sb0, sg1, sb1);
         Vec8<DT>::store(dx, idx, xv);
         if (POOL) {
 #pragma unroll

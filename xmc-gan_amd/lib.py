@@ -89,6 +89,8 @@ _SIGS = {
     "xmc_conv_ptile_scimg": [C.POINTER(ConvDesc), vp],
     "xmc_conv_wgrad_bits": [C.POINTER(ConvDesc), vp, vp],
     "xmc_gtail_bwd": [C.POINTER(ConvDesc), vp, vp, vp, i32, i32, vp],
+    "xmc_gentry_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp],
+    "xmc_gentry_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp],
     "xmc_tanh_bwd": [vp, vp, vp, i64, i32, vp],
     "xmc_axpby": [vp, vp, vp, vp, i64, i32, vp],
     "xmc_scale_mask_dot": [vp, vp, vp, vp, vp, i64, i32, vp],

@@ -788,6 +788,63 @@ def _affine_bwd_raw(x, dy, ps, slope, dx_acc=None, alpha=None, dot=None, want_su
     return (dx, red, dxp) if want_sumpool else (dx, red)
 
 
+def _gentry_accepts(x, geom, pair=False):
+    """whether the generator block entry kernels (xmc_gentry_fwd / xmc_gentry_bwd) take the case: 16-bit storage, a plain 1x1
+    shortcut at one of their channel pairs, not the precise trunk's weight pair, not switched off"""
+    return (x.is_cuda and x.dim() == 4 and x.dtype != torch.float32 and not pair and "no_gentry_fused" not in _DEBUG_DISPATCH
+            and geom.k == 1 and geom.s == 1 and geom.p == 0 and geom.groups == 1 and geom.row_perm is None
+            and geom.cin == x.shape[3] and (geom.cin, geom.cout) in ((64, 32), (128, 64), (256, 128)))
+
+
+def _gentry_fwd_raw(x, ps, w, bias, geom, pair=False, grid_cap=0):
+    """The entry of a generator block with a learned shortcut in one pass over x (xmc_gentry_fwd): -> (h, sc) with
+    h = lrelu(lrelu(x g0 + b0) g1 + b1), ps = (g0, b0, g1, b1) contiguous f32 [N, C], and sc = conv1x1(x, w) + bias (``bias``: f32
+    [cout] or None), or None when the kernel does not take the case -- the caller then runs `_affine_fwd_raw` and the 1x1
+    convolution, with the same results bit for bit."""
+    if not _gentry_accepts(x, geom, pair):
+        return None
+    _need_cuda(x, w)
+    N, H, W, Cc = x.shape
+    for t in ps:
+        assert t.shape == (N, Cc) and t.dtype == torch.float32 and t.is_contiguous(), (t.shape, (N, Cc))
+    assert x.is_contiguous() and len(ps) == 4
+    wpk = _packed_cached(w, geom, 0, x.dtype)
+    h = torch.empty_like(x)
+    sc = torch.empty((N, H, W, geom.cout), dtype=x.dtype, device=x.device)
+    with prof.launch("gentry_fwd_kernel (affine pair + 1x1 shortcut, one pass)", 2.0 * N * H * W * geom.cout * geom.cin,
+                     f"gentry-fwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(x, h, sc)):
+        rc = L.load().xmc_gentry_fwd(_p(x), *[_p(t) for t in ps], _p(wpk), _p(bias), _p(h), _p(sc), N, H, W, Cc, geom.cout,
+                                     wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st())
+    if rc == 1:
+        return None
+    L.check(rc, "xmc_gentry_fwd")
+    return h, sc
+
+
+def _gentry_bwd_raw(x, dy, dsc, ps, w, geom, want_sumpool=False, grid_cap=0):
+    """The backward of `_gentry_fwd_raw` in one pass (xmc_gentry_bwd): -> (dx, red [4, N, C], 2x2 sum pool of dx | None) from the
+    gradients ``dy`` of h and ``dsc`` of sc, as `_affine_bwd_raw(x, dy, ps, 0.2, dx_acc=conv1x1^T(dsc), want_sumpool=...)` gives them
+    (dx and its pool bit for bit, the sums in another order of additions), or None when the kernel does not take the case."""
+    N, H, W, Cc = x.shape
+    if not _gentry_accepts(x, geom) or (want_sumpool and (H % 2 or W % 2)):
+        return None
+    _need_cuda(x, dy, dsc, w)
+    assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
+    assert dsc.shape == (N, H, W, geom.cout) and dsc.dtype == x.dtype and dsc.is_contiguous() and len(ps) == 4
+    wpk = _packed_cached(w, geom, 1, x.dtype)
+    dx = torch.empty_like(x)
+    dxp = torch.empty((N, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device) if want_sumpool else None
+    red = _zeros_f32((4, N, Cc), x.device)
+    with prof.launch("gentry_bwd_kernel (1x1 shortcut dgrad + affine pair backward, one pass)", 2.0 * N * H * W * geom.cout * geom.cin,
+                     f"gentry-bwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(x, dy, dsc, dx, dxp)):
+        rc = L.load().xmc_gentry_bwd(_p(x), _p(dy), _p(dsc), *[_p(t) for t in ps], _p(wpk), _p(dx), _p(dxp), *[_p(red[i]) for i in range(4)],
+                                     N, H, W, Cc, geom.cout, wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st())
+    if rc == 1:
+        return None
+    L.check(rc, "xmc_gentry_bwd")
+    return dx, red, dxp
+
+
 # ------------------------------------------------------------------------------------------ discriminator stem (csrc/dstem.hip)
 def compose_dstem(w_img, b_img, w0, ws, bs):
     """conv_img followed (without an activation) by the first resD block's conv_r[0] and by its pooled 1x1 shortcut, as ONE set of

@@ -6,8 +6,8 @@ from ._config import _DEBUG_DISPATCH, _code, _need_cuda, _p, _second_order, _ski
 from ._engine import (
     _StagedMask, _affine_bwd_raw, _affine_fwd_raw, _conv1x1_pair_raw, _conv_dgrad_raw, _conv_fwd_raw, _conv_wgrad_raw,
     _dstem_border_fwd_raw, _dstem_compose_bwd_raw, _dstem_compose_raw, _dstem_dgrad_raw, _dstem_fwd_raw, _dstem_sc_operands,
-    _dstem_wgrad_raw, _pooled_put, _zeros_f32, _zeros_f32_out)
-from ._nodes_leaf import CastFn
+    _dstem_wgrad_raw, _gentry_accepts, _gentry_bwd_raw, _gentry_fwd_raw, _pooled_put, _zeros_f32, _zeros_f32_out)
+from ._nodes_leaf import CastFn, ColSumFn
 from ._nodes_conv import _bias_padded
 
 
@@ -527,6 +527,74 @@ class Affine2LreluSkipFn(torch.autograd.Function):
 
 def affine2_lrelu_skip(x, g0, b0, g1, b1, pool_grad=False):
     return Affine2LreluSkipFn.apply(x, g0, b0, g1, b1, pool_grad)
+
+
+class GBlockEntryFn(torch.autograd.Function):
+    """The entry of a generator block with a learned shortcut (df_gan.py:199-216 with in_dim != out_dim): (h, sc) =
+    (lrelu(lrelu(x g0 + b0) g1 + b1), c_sc(x)) from ONE pass over x (xmc_gentry_fwd), where Affine2LreluSkipFn + the shortcut's ConvFn read
+    x twice.  The backward is one pass as well (xmc_gentry_bwd): the shortcut's data gradient is formed per pixel group inside the
+    affine backward and never written; c_sc's weight and bias gradient come from the 1x1 weight-gradient launch as ever.  Same
+    values as that pair of nodes: h, sc, dx and its pool bit for bit, the four sums in another order of additions."""
+
+    @staticmethod
+    def forward(ctx, x, g0, b0, g1, b1, w, b, geom, pool_grad=False):
+        """``pool_grad``: x came out of a GBlockEndFn -- the backward pools its dx for that node (ops._pooled_grads)"""
+        x = x.contiguous()
+        ps = [t.contiguous().float() for t in (g0, b0, g1, b1)]
+        r = _gentry_fwd_raw(x, ps, w, _bias_padded(b, geom), geom)
+        if r is None:
+            raise RuntimeError("GBlockEntryFn: not a case of xmc_gentry_fwd (ask ops.g_block_entry, which returns None for those)")
+        ctx.set_materialize_grads(False)
+        ctx.geom, ctx.pool, ctx.has_b = geom, bool(pool_grad), b is not None
+        ctx.save_for_backward(x, w, *ps)
+        return r
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, dsc):
+        x, w, *ps = ctx.saved_tensors
+        geom = ctx.geom
+        if dy is None and dsc is None:
+            return (None,) * 9
+        if dsc is not None:
+            dsc = dsc.contiguous()
+        dx, red = None, (None,) * 4
+        if dy is None:            # the shortcut's gradient alone, as Affine2LreluSkipFn hands it through
+            if ctx.needs_input_grad[0]:
+                dx = _conv_dgrad_raw(dsc, w, geom, (x.shape[1], x.shape[2]), x.dtype)
+        else:
+            dy = dy.contiguous()
+            pool = ctx.pool and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
+            # x is the output of the previous generator block, whose backward needs the 2x2 sum pool of this gradient
+            r = _gentry_bwd_raw(x, dy, dsc, ps, w, geom, want_sumpool=pool) if dsc is not None else None
+            if r is None:         # no shortcut gradient, or switched off since the forward: the affine backward [and the 1x1 data gradient]
+                dskip = _conv_dgrad_raw(dsc, w, geom, (x.shape[1], x.shape[2]), x.dtype) if dsc is not None else None
+                r = _affine_bwd_raw(x, dy, ps, 0.2, dx_acc=dskip, want_sumpool=pool)
+                r = r if pool else (*r, None)
+            dx, red, dxp = r
+            if pool:
+                _pooled_put(dx, dxp)
+        dw = db = None
+        if dsc is not None and not _skip_wgrad():
+            want_b = ctx.has_b and ctx.needs_input_grad[6]
+            if ctx.needs_input_grad[5]:         # (the bias gradient rides on the weight-gradient launch)
+                gw = _conv_wgrad_raw(x, dsc, geom, want_bias=want_b)
+                dw, db = gw if want_b else (gw, None)
+                dw = dw.view(w.shape)
+            elif want_b:
+                db = ColSumFn.apply(dsc)
+            if db is not None:
+                db = db[: geom.cout]
+        return dx, red[0], red[1], red[2], red[3], dw, db, None, None
+
+
+def g_block_entry(x, mod4, w, b, geom, pool_grad=False, pair=False):
+    """(h, sc) of a generator block's entry (GBlockEntryFn), or None where its kernels do not take the case (f32 storage, the precise
+    trunk's weight pair, other channel counts, XMC_DEBUG_DISPATCH=no_gentry_fused): the caller then runs `affine2_lrelu_skip` and the
+    shortcut convolution."""
+    if not _gentry_accepts(x, geom, pair):
+        return None
+    return GBlockEntryFn.apply(x, *mod4, w, b, geom, pool_grad)
 
 
 class GroupNormFn(torch.autograd.Function):

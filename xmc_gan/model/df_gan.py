@@ -298,20 +298,30 @@ class G_Block(nn.Module):
             return ops.lrelu(out) if out_lrelu else out
         # x feeds the residual branch AND the shortcut: the affine node hands x through as a second output, so that the two
         # gradients of x are summed inside its backward kernel
-        h, xs = ops.affine2_lrelu_skip(x, *mod[0:4], pool_grad=x_from_end) if x.is_cuda else (ops.affine2_lrelu(x, *mod[0:4]), x)
+        # a learned shortcut: the affine pair and c_sc in one pass over x, forward and backward (ops.GBlockEntryFn; None where its
+        # kernels do not take the case: f32 storage, the precise trunk's weight pair, other channel counts)
+        entry = None
+        if self.learnable_sc and x.is_cuda and not self.c_sc.spec_norm:
+            entry = ops.g_block_entry(x, mod[0:4], self.c_sc.weight, self.c_sc.bias, self.c_sc.geom, x_from_end, pair=ops.precise_trunk())
+        if entry is not None:
+            h, sc = entry
+        else:
+            h, xs = ops.affine2_lrelu_skip(x, *mod[0:4], pool_grad=x_from_end) if x.is_cuda else (ops.affine2_lrelu(x, *mod[0:4]), x)
+            sc = None
+        shortcut = (lambda: self.shortcut(xs)) if sc is None else (lambda: sc)
         h = ops.upconv3x3(h, self.c1.weight, self.c1.bias, self.c1.geom)
         if self.fuses_end(x, x_pending_up) and (tail is not None or not out_lrelu):
             # affine2/3 + LeakyReLUs, c2, the block sum with the upsampled shortcut [, the tail] in one node whose backward
             # needs neither c2's output nor a separate pass for gamma * dout (ops.GBlockEndFn)
-            return ops.g_block_end(h, mod[4:8], self.c2.weight, self.c2.bias, self.c2.geom, self.shortcut(xs), self.gamma,
+            return ops.g_block_end(h, mod[4:8], self.c2.weight, self.c2.bias, self.c2.geom, shortcut(), self.gamma,
                                    tail=tail, nhwc_dst=nhwc_dst)
         assert tail is None
         h = ops.affine2_lrelu(h, *mod[4:8])
         if not out_lrelu and ops.fused_blocks() and h.shape[1] % 2 == 0:
             # c2, the block sum and the upsample of the shortcut in one pass (third epilogue form, res_mode 2)
-            return ops.conv_axpby_up(h, self.c2.weight, self.c2.bias, self.c2.geom, self.shortcut(xs), self.gamma)
+            return ops.conv_axpby_up(h, self.c2.weight, self.c2.bias, self.c2.geom, shortcut(), self.gamma)
         # out_lrelu: the tail's LeakyReLU (df_gan.py:84-85) applied while the block sum is written
-        return ops.axpby_up(self.shortcut(xs), self.c2(h), self.gamma, lrelu=out_lrelu)
+        return ops.axpby_up(shortcut(), self.c2(h), self.gamma, lrelu=out_lrelu)
 
     def shortcut(self, x):
         # precise trunk (IEEE-half mode, ops.precise_trunk): the image is, to first order in the block gammas, a function of the shortcut
