@@ -31,7 +31,7 @@ extern "C" {
  *    xmc_adam_step gained grad_scale.
  * 4: XmcConvDesc.sign_bits / dot (a discriminator block keeps sign bits; d(gamma) from a data-gradient epilogue).
  * 5: xmc_conv_pw1x1_masked_src (the sign-mask pass as a by-product of the shortcut's data gradient).
- * 6: xmc_adam_step_scaled (dynamic loss scale with a found-inf skip); xmc_gp_finish gained inv_s2.
+ * 6: xmc_adam_step_scaled: dynamic loss scale with a found-inf skip; xmc_gp_finish gained inv_s2.
  * 7: xmc_dstem_* (the discriminator's stem composed into one convolution from the image).
  * 8: XmcConvDesc.mask_bits, xmc_conv_ptile_bits / xmc_conv_wgrad_bits (the sign mask applied in the consumers' staging).
  * 9: XmcConvDesc.sc_img / sc_frag / sc_bias, xmc_conv_ptile_scimg, xmc_dstem_pack_sc (the stem block's shortcut recomputed from the image in
@@ -56,8 +56,15 @@ extern "C" {
  *     xmc_gentry_fwd / xmc_gentry_bwd (csrc/conv_thin.hip: a generator block's affine pair and learned 1x1 shortcut in one pass each);
  *     xmc_caption_gather (csrc/captionfeed.hip);
  *     xmc_manifold_slices / xmc_row_sqnorm / xmc_knn_radius2 / xmc_manifold_count (csrc/manifold.hip);
- *     xmc_poly_mmd_tiles / xmc_poly_mmd_sums / xmc_inception_score_ws_bytes / xmc_inception_score (csrc/kid.hip). */
-#define XMC_ABI_VERSION 12
+ *     xmc_poly_mmd_tiles / xmc_poly_mmd_sums / xmc_inception_score_ws_bytes / xmc_inception_score (csrc/kid.hip).
+ * 13: one exported name per launch; names that only forwarded to a wider one are gone.
+ *     Removed: xmc_affine2_lrelu_fwd / _bwd: call xmc_affine2_act_* with slope 0.2; xmc_avgpool2: call xmc_sumpool2 with scale 0.25;
+ *     xmc_pack_weight / _grouped / _upconv: hand one XmcPackJob to xmc_pack_weight_multi.
+ *     Merged, the widest argument list under the shortest name, every optional pointer nullable:
+ *     xmc_affine2_act_bwd <- _acc / _dot / _dot_pool (now takes N, H, W);  xmc_attn_pool_bwd <- _acc (dx_acc);
+ *     xmc_conv_wgrad <- _bias (dbias);  xmc_unpack_wgrad <- _grouped / _bias / _bias_dot (groups, gb_replicas, gb, CD, bias_dot, dot).
+ *     XmcOptimStep + xmc_optim_step replace xmc_adam_step, xmc_adam_step_scaled, xmc_adam_ema_step and xmc_adam_ema_step_scaled. */
+#define XMC_ABI_VERSION 13
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
  * libxmc_gan_hip.so, IEEE half in libxmc_gan_hip_f16.so (same sources, same entry points; xmc_half_format()). */
@@ -127,7 +134,7 @@ typedef struct XmcConvDesc {
     /* round_act != 0 (implied by dst2): act(acc + bias) is rounded to the dst dtype before alpha / mask / residual, so that a
      * fused block sum equals, bit for bit, the unfused sequence that stores the residual branch first. */
     int32_t round_act;
-    /* groups > 1: wpk is the block-diagonal expansion of an nn.Conv2d(groups=g) weight (xmc_pack_weight_grouped); kernels that
+    /* groups > 1: wpk is the block-diagonal expansion of an nn.Conv2d(groups=g) weight (XmcPackJob.groups); kernels that
      * know the structure skip the zero blocks (conv_group.hip), the others multiply them.  0 is read as 1. */
     int32_t groups;
     /* post_act (XMC_ACT_NONE / XMC_ACT_LRELU): an activation applied LAST, after alpha / mask / residual -- the LeakyReLU in front
@@ -179,7 +186,7 @@ const char* xmc_last_kernel(void);
 /* test mode: the reductions that feed activations (GroupNorm statistics, the attention query gradient) run with one workgroup per
  * reduction target, i.e. in a fixed summation order; returns the previous setting (ABI 10) */
 int xmc_set_fixed_order(int on);
-/* Accumulators the entry points below document as "zeroed here" -- xmc_groupnorm_fwd / _bwd `ws`, xmc_attn_pool_bwd_acc `dq`,
+/* Accumulators the entry points below document as "zeroed here" -- xmc_groupnorm_fwd / _bwd `ws`, xmc_attn_pool_bwd `dq`,
  * xmc_global_avgpool's f32 `y` on maps of >= 256 pixels,
  * xmc_word_pool_fwd `ctx` / _bwd `dkh`, xmc_concept_query_bwd_multi `dsent`, xmc_concept_outer_multi `dX` -- are cleared with a hipMemsetAsync of their own, one more launch per call
  * (~100 per iteration of an attention-modulation generator).  on = 1: the caller promises they arrive ALREADY ZERO (the Python host
@@ -198,26 +205,25 @@ int xmc_conv_igemm(const XmcConvDesc* d, void* stream);
  *   dwp[t][co][ci] += sum_{n,a,b} dy[n,a,b,co] * x[n, a*SA+dh[t], b*SA+dw[t], ci]      (f32, atomically accumulated;
  * the caller zeroes dwp).  x: [N,SH,SW,CS], dy: [N,MH,MW,CD].  Uses class 0 of the tap table.
  */
-int xmc_conv_wgrad(const XmcConvDesc* d /* src=x, dst=dy (read only) */, float* dwp, void* stream);
-/* same launch, additionally the bias gradient (sum over all pixels of dy[.,co]) without an extra pass over dy.  To keep the
- * atomics off a single cache line, workgroups add into XMC_BIAS_REPLICAS replicas: dbias is f32 [XMC_BIAS_REPLICAS][CD],
- * zeroed by the caller, and the caller sums the replicas. */
+/* dbias != NULL: the same launch additionally forms the bias gradient (sum over all pixels of dy[.,co]) without an extra pass
+ * over dy.  To keep the atomics off a single cache line, workgroups add into XMC_BIAS_REPLICAS replicas: dbias is
+ * f32 [XMC_BIAS_REPLICAS][CD], zeroed by the caller, and the caller sums the replicas (xmc_unpack_wgrad).  NULL: no bias gradient. */
 #define XMC_BIAS_REPLICAS 16
-int xmc_conv_wgrad_bias(const XmcConvDesc* d, float* dwp, float* dbias, void* stream);
+int xmc_conv_wgrad(const XmcConvDesc* d /* src=x, dst=dy (read only) */, float* dwp, float* dbias, void* stream);
 
 /* ---- weight (un)packing between nn.Parameter layout [Co][Ci][KH][KW] f32 and kernel layouts --------------- */
-/* fwd pack:  wpk[kh*KW+kw][co][ci]      (rows padded to CDw, cols to CSp, zeros)                               */
-/* dgrad pack: wpk[kh*KW+kw][ci][co]     (rows padded to CSw, cols to CDp)                                       */
-int xmc_pack_weight(const float* w, void* wpk, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                    int transpose /*0 fwd, 1 dgrad*/, int dtype, const int32_t* row_perm /*NULL or [Co]*/, void* stream);
-/* same for an nn.Conv2d(groups=g) weight [Co][Ci/g][KH][KW] (df_concept_gan.py:146,267,546: 16 groups of 8 channels): the packed
- * matrix is the block-diagonal expansion; xmc_unpack_wgrad_grouped reads the diagonal blocks back into gw [Co][Ci/g][KH][KW] */
-int xmc_pack_weight_grouped(const float* w, void* wpk, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad, int transpose,
-                            int dtype, const int32_t* row_perm, int groups, void* stream);
-int xmc_unpack_wgrad_grouped(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                             const float* scale_dev, const int32_t* row_perm, int accumulate, int groups, void* stream);
-/* Any number of the packs above (and of xmc_pack_weight_upconv below: upconv != 0, KHW ignored) in one launch per
- * XMC_PACK_MULTI_MAX jobs: the optimizer step re-packs every cached copy of the weights it changed (ops.repack_params). */
+/* One job of xmc_pack_weight_multi:
+ *   fwd pack   (transpose 0): wpk[t][co][ci], t < KHW = KH*KW   (rows padded to rows_pad = CDw, cols to cols_pad = CSp, zeros)
+ *   dgrad pack (transpose 1): wpk[t][ci][co]                    (rows padded to CSw, cols to CDp)
+ *   row_perm (NULL or [Co]): packed row r holds parameter row row_perm[r].
+ *   groups > 1: w is an nn.Conv2d(groups=g) weight [Co][Ci/g][KH][KW] (df_concept_gan.py:146,267,546: 16 groups of 8 channels) and
+ *   the packed matrix is its block-diagonal expansion; xmc_unpack_wgrad with the same `groups` reads the diagonal blocks back.
+ *   upconv != 0 (KHW ignored; groups 1, no row_perm): fused nearest-x2 upsample + 3x3 conv (F.interpolate(scale_factor=2) at
+ *   df_gan.py:202 followed by the next block's c1, 187): 16 slices wpk[(i*2+j)*4 + th*2+tw][...] of pre-summed weights, one 2x2-tap
+ *   convolution per output parity (i,j) on the LOW-resolution tensor -> 4/9 of the MACs and no materialised upsampled tensor.  Used
+ *   with a 4-class tap table.
+ * Any number of jobs in one launch per XMC_PACK_MULTI_MAX: the optimizer step re-packs every cached copy of the weights it changed
+ * (ops.repack_params). */
 #define XMC_PACK_MULTI_MAX 48
 typedef struct XmcPackJob {
     const float* w;
@@ -227,24 +233,17 @@ typedef struct XmcPackJob {
     int32_t lo;             /* ABI 12: 1 = pack round16(w - round16(w)) (XmcConvDesc.wpk_lo) instead of round16(w); 16-bit dtype only */
 } XmcPackJob;
 int xmc_pack_weight_multi(const XmcPackJob* jobs /* host array */, int njobs, void* stream);
-/* Fused nearest-x2 upsample + 3x3 conv (F.interpolate(scale_factor=2) at df_gan.py:202 followed by the next block's c1, 187):
- * 16 slices wpk[(i*2+j)*4 + th*2+tw][...] of pre-summed weights, one 2x2-tap convolution per output parity (i,j) on the
- * LOW-resolution tensor -> 4/9 of the MACs and no materialised upsampled tensor.  Used with a 4-class tap table. */
-int xmc_pack_weight_upconv(const float* w, void* wpk, int Co, int Ci, int rows_pad, int cols_pad, int transpose, int dtype,
-                           void* stream);
-/* grad unpack: gw[co][ci][kh][kw] (+)= scale * dwp[kh*KW+kw][co][ci] (dwp rows padded to rows_pad, cols to cols_pad) */
+/* grad unpack: gw[co][ci][kh][kw] (+)= scale * dwp[kh*KW+kw][co][ci] (dwp rows padded to rows_pad, cols to cols_pad).
+ *   scale_dev NULL: scale 1.  row_perm NULL: packed row r is parameter row r.  groups > 1: gw is [Co][Ci/groups][KH][KW], the
+ *   diagonal blocks of the dense gradient.
+ *   gb_replicas / gb (both or neither; groups must be 1): gb[c] = scale * sum over the XMC_BIAS_REPLICAS rows of gb_replicas[r][c]
+ *   (c < CD): the bias gradient xmc_conv_wgrad accumulated, reduced in the same launch.  NULL: no bias gradient, CD ignored.
+ *   bias_dot / dot (both or neither; need the bias output and no row_perm): *dot += sum_c bias_dot[c] * (the UNSCALED bias gradient c),
+ *   c < Co: the bias term of d(alpha) of a layer y = alpha * (conv(x) + bias) whose output is not kept (xmc_affine2_act_bwd's
+ *   alpha_dev / dot).  NULL: no such term. */
 int xmc_unpack_wgrad(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                     const float* scale_dev, const int32_t* row_perm, int accumulate, void* stream);
-/* same, and gb[c] = sum over the XMC_BIAS_REPLICAS rows of gb_replicas[r][c] (c < CD): the bias gradient xmc_conv_wgrad_bias
- * accumulated, reduced in the same launch */
-int xmc_unpack_wgrad_bias(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                          const float* scale_dev, const int32_t* row_perm, int accumulate,
-                          const float* gb_replicas, float* gb, int CD, void* stream);
-/* same, and *dot += sum_c bias_dot[c] * (the UNSCALED bias gradient c), c < Co: the bias term of d(alpha) of a layer
- * y = alpha * (conv(x) + bias) whose output is not kept (xmc_affine2_act_bwd_dot); bias_dot and dot both NULL = the call above */
-int xmc_unpack_wgrad_bias_dot(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                              const float* scale_dev, const int32_t* row_perm, int accumulate,
-                              const float* gb_replicas, float* gb, int CD, const float* bias_dot, float* dot, void* stream);
+                     const float* scale_dev, const int32_t* row_perm, int accumulate, int groups,
+                     const float* gb_replicas, float* gb, int CD, const float* bias_dot, float* dot, void* stream);
 
 /* ---- layout conversion at the module boundary (NetD.forward input df_gan.py:127, NetG output df_gan.py:101) -- */
 int xmc_nchw_to_nhwc8(const float* src /*[N,C,H,W] f32*/, void* dst /*[N,H,W,8]*/, int N, int C, int H, int W,
@@ -285,9 +284,9 @@ int xmc_conv_wgrad_bits(const XmcConvDesc* d, float* dwp, void* stream);
  * dpre = dy * (1 - img^2), rounded as xmc_tanh_bwd rounds it, where it stages the operand.  d->dst / d->dst_pool receive what
  * xmc_tanh_bwd + xmc_conv_igemm write today, bit for bit.  dwp != NULL: also conv_out's weight gradient, accumulated into
  * dwp f32 [9][dw_rows][32] (the packed layout of xmc_conv_wgrad, rows 0..3 of each tap; zeroed by the caller), and with dbias != NULL
- * its bias gradient into f32 [XMC_BIAS_REPLICAS][8] (as xmc_conv_wgrad_bias).  grid_cap > 0 limits the persistent grid
+ * its bias gradient into f32 [XMC_BIAS_REPLICAS][8] (as xmc_conv_wgrad).  grid_cap > 0 limits the persistent grid
  * (tests: several tiles per workgroup on small maps).  Returns 1 and launches nothing for what the kernel does not take (f32, y channels != 32, H % 8 != 0, odd W, a
- * descriptor with bias / act / res / ...; XMC_DEBUG_DISPATCH=no_gtail_fused): the caller then runs xmc_tanh_bwd, xmc_conv_wgrad_bias
+ * descriptor with bias / act / res / ...; XMC_DEBUG_DISPATCH=no_gtail_fused): the caller then runs xmc_tanh_bwd, xmc_conv_wgrad
  * and xmc_conv_igemm. */
 int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, float* dbias, int dw_rows, int grid_cap, void* stream);
 /* The entry of a generator block with a learned shortcut (G_Block with in_dim != out_dim), one pass over the block input x [N,H,W,Cin] per
@@ -295,7 +294,7 @@ int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, float* dbia
  * xmc_gentry_fwd: h = lrelu(lrelu(x g0 + b0) g1 + b1) (xmc_affine2_act_fwd's bits) and sc = conv1x1(x, wpk) + bias [N,H,W,Cout] (the
  * streaming 1x1 kernels' bits) from one load of x.  wpk: the forward pack [1][wrows = Cout][Cin]; bias f32 [Cout] or NULL.
  * xmc_gentry_bwd: dskip = conv1x1^T(dsc) is formed per 16-pixel group, rounded to the storage format and never written; then everything
- * xmc_affine2_act_bwd_dot_pool does with dx_in = dskip: dx (bit for bit), the four sums dg0 / db0 / dg1 / db1 (f32 [N,Cin], ACCUMULATED:
+ * xmc_affine2_act_bwd does with dx_in = dskip: dx (bit for bit), the four sums dg0 / db0 / dg1 / db1 (f32 [N,Cin], ACCUMULATED:
  * zeroed by the caller; another order of additions than the affine kernel's) and, with dx_pool != NULL, the 2x2 sum pool of the rounded
  * dx [N,H/2,W/2,Cin].  wpk_t: the data-gradient pack [1][wrows = Cin][Cout].  The fixed-order mode does not apply (as for the affine
  * backward).  grid_cap > 0 limits the persistent grid (tests).  Both return 1 and launch nothing for what they do not take: f32 storage,
@@ -404,10 +403,9 @@ int xmc_axpby_bwd(const void* dy, const void* b, const float* alpha_dev, void* d
                   (then da is also written in the plain form: the masked dy) */, int dtype, void* stream);
 /* out[c] = sum over rows of x[r][c]         (bias gradients) ; out is f32 [C], zeroed by the caller */
 int xmc_colsum(const void* x, float* out, int64_t rows, int C, int dtype, void* stream);
-/* 2x2 average pool (F.avg_pool2d(x,2) df_gan.py:290) and its adjoint (nearest x2 upsample * scale) */
-int xmc_avgpool2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
+/* nearest x2 upsample * scale: the adjoint of the 2x2 average pool (F.avg_pool2d(x,2) df_gan.py:290) with scale 0.25 */
 int xmc_upsample2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* stream);
-/* 2x2 sum pool * scale  (adjoint of nearest upsample, F.interpolate df_gan.py:202) == avgpool2 with scale 4*scale */
+/* 2x2 sum pool * scale  (adjoint of nearest upsample, F.interpolate df_gan.py:202); scale 0.25 = the average pool itself */
 int xmc_sumpool2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* stream);
 /* global average over HW -> [N,C] (F.avg_pool2d(x,4) on 4x4 maps df_gan.py:165, train_gan.py:272,275) + adjoint */
 int xmc_global_avgpool(const void* x, void* y, int N, int HW, int C, int dtype, int out_dtype, void* stream);
@@ -418,38 +416,25 @@ int xmc_global_avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, int d
  * LeakyReLU(0.2) after each, as used at df_gan.py:213-216 and 219-222):
  *   y = lrelu( lrelu(x*g0 + b0) * g1 + b1 ),   g*,b* : f32 [N,C] (per sample, per channel)
  * backward returns dx and the four [N,C] f32 reductions (zeroed by the caller; atomically accumulated).
+ * slope: the activation's; 0.2 for the DF-GAN blocks, 0 = ReLU, the activation of the word-attention generator's conditional
+ * BatchNorm / concept modulation (concept_gan.py:419-421,446-447,496-497,508-509).
  */
-int xmc_affine2_lrelu_fwd(const void* x, const float* g0, const float* b0, const float* g1, const float* b1,
-                          void* y, int N, int HW, int C, int dtype, void* stream);
-int xmc_affine2_lrelu_bwd(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                          const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                          int N, int HW, int C, int dtype, void* stream);
-
-/* the same with the activation slope as an argument: slope 0 = ReLU, the activation of the word-attention generator's
- * conditional BatchNorm / concept modulation (concept_gan.py:419-421,446-447,496-497,508-509) */
 int xmc_affine2_act_fwd(const void* x, const float* g0, const float* b0, const float* g1, const float* b1,
                         void* y, int N, int HW, int C, float slope, int dtype, void* stream);
+/* The optional arguments of the backward, each NULL = that part is absent:
+ *  dx_in    : another gradient of x (dx layout, may alias dx), added on the way out: x feeds the block's shortcut as well
+ *             (df_gan.py:199-200), and its gradient would otherwise meet this one in a separate add pass.
+ *  alpha_dev / dot (both or neither): for a consumer y -> sum + alpha * f(y) whose backward hands over dy = d loss / d f's input
+ *             UNSCALED (df_gan.py:200-202: `shortcut + gamma * c2(y)`): *dot += <dy, y> (y = this node's forward output,
+ *             recomputed; d(alpha) up to f's bias term) and dy is multiplied by *alpha_dev before use.
+ *  dx_pool  : [N, H/2, W/2, C] = the 2x2 sum pool of the dx this call writes (each dx rounded as stored): the gradient of the
+ *             half-resolution shortcut of the generator block that produced x (the adjoint of F.interpolate(scale_factor=2),
+ *             df_gan.py:200-202), written in the same pass.  Needs even H and W and C / 8 a power of two <= 32.
+ * Without dx_pool only the product H * W matters. */
 int xmc_affine2_act_bwd(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                        const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                        int N, int HW, int C, float slope, int dtype, void* stream);
-/* ... with another gradient of x (dx_in, dx layout, may alias dx) added on the way out: x feeds the block's shortcut as well
- * (df_gan.py:199-200), and its gradient would otherwise meet this one in a separate add pass */
-int xmc_affine2_act_bwd_acc(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                            const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1, const void* dx_in,
-                            int N, int HW, int C, float slope, int dtype, void* stream);
-/* ... for a consumer y -> sum + alpha * f(y) whose backward hands over dy = d loss / d f's input UNSCALED (df_gan.py:200-202:
- * `shortcut + gamma * c2(y)`): *dot += <dy, y> (y = this node's forward output, recomputed; d(alpha) up to f's bias term) and
- * dy is multiplied by *alpha_dev before use.  alpha_dev and dot both NULL = the call above. */
-int xmc_affine2_act_bwd_dot(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                            const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1, const void* dx_in,
-                            const float* alpha_dev, float* dot, int N, int HW, int C, float slope, int dtype, void* stream);
-/* ... and dx_pool [N, H/2, W/2, C] (optional) = the 2x2 sum pool of the dx this call writes (each dx rounded as stored): the
- * gradient of the half-resolution shortcut of the generator block that produced x (the adjoint of F.interpolate(scale_factor=2),
- * df_gan.py:200-202), written in the same pass */
-int xmc_affine2_act_bwd_dot_pool(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                 const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1, const void* dx_in,
-                                 const float* alpha_dev, float* dot, void* dx_pool, int N, int H, int W, int C, float slope,
-                                 int dtype, void* stream);
+                        const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1, const void* dx_in,
+                        const float* alpha_dev, float* dot, void* dx_pool, int N, int H, int W, int C, float slope,
+                        int dtype, void* stream);
 /* single-stage form of the same kernels: pass g1 = b1 = NULL (and dg1 = db1 = NULL) -> y = lrelu(x*g0 + b0), the
  * concept blocks' modulation `gamma * img_embs + beta` + LeakyReLU (df_concept_gan.py:238-239,250-251) */
 
@@ -463,7 +448,7 @@ int xmc_affine2_act_bwd_dot_pool(const void* x, const void* dy, const float* g0,
  *   key [N][HW][ncon*pk], x [N][HW][ncon*px] (activation dtype); q [N][ncon][pk], ctx [N][ncon][px] f32; ncon = 16, pk = 4, px = 8.
  *   The attention weights are not materialised: fwd leaves stats [N][ncon][2] = (max_p score, sum_p exp(score - max)) from which
  *   bwd recomputes them; ws: xmc_attn_pool_ws_floats(N, HW) floats of scratch for fwd.  bwd writes dq, dkey, dx (dkey / dx:
- *   every element exactly once).
+ *   every element exactly once).  dx_acc (NULL: none): another gradient of x (dx layout; may alias dx), added on the way out.
  */
 int xmc_groupnorm_fwd(const void* x, const float* w, const float* b, void* y, float* stats, float* ws,
                       int N, int HW, int C, int G, float eps, float slope, int dtype, void* stream);
@@ -473,11 +458,8 @@ int64_t xmc_attn_pool_ws_floats(int N, int HW);
 int xmc_attn_pool_fwd(const void* key, const float* q, const void* x, float* stats, float* ctx, float* ws, int N, int HW,
                       int ncon, int pk, int px, float scale, int dtype, void* stream);
 int xmc_attn_pool_bwd(const void* key, const float* q, const void* x, const float* stats, const float* ctx, const float* dctx,
-                      float* dq, void* dkey, void* dx, int N, int HW, int ncon, int pk, int px, float scale, int dtype, void* stream);
-/* same, with another gradient of x (dx_in, dx layout; may alias dx) added on the way out */
-int xmc_attn_pool_bwd_acc(const void* key, const float* q, const void* x, const float* stats, const float* ctx, const float* dctx,
-                          float* dq, void* dkey, void* dx, const void* dx_in, int N, int HW, int ncon, int pk, int px, float scale,
-                          int dtype, void* stream);
+                      float* dq, void* dkey, void* dx, const void* dx_acc, int N, int HW, int ncon, int pk, int px, float scale,
+                      int dtype, void* stream);
 
 /* ---- per-concept algebra of the word-attention generators (model/concept_gan.py; C = 16 concepts, P = 4 state channels, f32) ----
  * Grouped 1x1 convolution of a per-sample vector: y[b,g,o] = bias[g,o] + sum_{i<Is} W[g,o,i] xs[b,i] + sum_{i<Ig} W[g,o,Is+i] xg[b,g,i],
@@ -543,7 +525,7 @@ int xmc_cast(const void* x, void* y, int64_t n, int src_dtype, int dst_dtype, vo
 
 /*
  * Multi-tensor Adam (torch.optim.Adam.step as used at train_gan.py:229,252,289; eps 1e-8, no weight decay):
- * one launch updates every tensor of `table_dev` (DEVICE array).  `chunks_dev` is a DEVICE array of
+ * one launch (xmc_optim_step, below) updates every tensor of `table` (DEVICE array).  `chunks` is a DEVICE array of
  * nchunks (tensor index, chunk index) int32 pairs, one per block, chunk = xmc_adam_chunk_elems() elements.
  * `step` is a device counter per tensor holding the number of updates already applied; the launch uses
  * step+1 for the bias corrections and then increments it, so the whole call is hipGraph-replayable.
@@ -559,19 +541,14 @@ typedef struct XmcAdamEntry {
     int64_t n;
 } XmcAdamEntry;
 int xmc_adam_chunk_elems(void);
-int xmc_adam_step(const XmcAdamEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks,
-                  float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
-/* The same update under a DYNAMIC loss scale (the IEEE-half mode; the reference is f32 and has none -- the rule is
- * torch.cuda.amp.GradScaler's).  scale_dev: float[2] = {scale, 1 / scale}; flags_dev: int32[4] = {a gradient of this step is
- * not finite, consecutive finite steps, that flag at the last finished step, steps skipped so far}.  `mode` is a set of phases,
- * run in this order: XMC_ADAM_CHECK raises the flag if any gradient element of the table is inf / NaN; XMC_ADAM_UPDATE reads the
- * gradients times 1 / scale and updates -- NOTHING (parameters, moments, step counters) while the flag is up; XMC_ADAM_RESCALE
- * ends an optimizer step: scale x backoff after a skipped step, x growth after `interval` finite steps in a row, flag cleared.
- * (An optimizer with several parameter groups checks all of them before it updates any.)  All on the device: capturable. */
+/* Under a DYNAMIC loss scale (the IEEE-half mode; the reference is f32 and has none -- the rule is torch.cuda.amp.GradScaler's):
+ * scale_dev: float[2] = {scale, 1 / scale}; flags_dev: int32[4] = {a gradient of this step is not finite, consecutive finite
+ * steps, that flag at the last finished step, steps skipped so far}.  `mode` is a set of phases, run in this order:
+ * XMC_ADAM_CHECK raises the flag if any gradient element of the table is inf / NaN; XMC_ADAM_UPDATE reads the gradients times
+ * 1 / scale and updates -- NOTHING (parameters, moments, step counters) while the flag is up; XMC_ADAM_RESCALE ends an optimizer
+ * step: scale x backoff after a skipped step, x growth after `interval` finite steps in a row, flag cleared.  (An optimizer with
+ * several parameter groups checks all of them before it updates any.)  All on the device: capturable. */
 enum { XMC_ADAM_CHECK = 1, XMC_ADAM_UPDATE = 2, XMC_ADAM_RESCALE = 4 };
-int xmc_adam_step_scaled(const XmcAdamEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks,
-                         float lr, float beta1, float beta2, float eps, float* scale_dev, int32_t* flags_dev,
-                         int mode, float growth, float backoff, int interval, void* stream);
 
 /*
  * Exponential moving average of a network's weights (the "shadow" set a GAN is sampled from at evaluation time; the reference
@@ -580,7 +557,7 @@ int xmc_adam_step_scaled(const XmcAdamEntry* table_dev, int ntensors, const int3
  *     e = e + (1 - d) * (p - e)            (f32; an element with e == p is a fixed point, bit for bit)
  * `num_updates_dev` is ONE device int32 for the whole shadow set, the number of updates already applied; warm-up or averaging
  * is decided on the device from it, so a captured call crosses `start` without re-capture.  `table_dev` is a DEVICE array of
- * ntensors entries, `chunks_dev` the (tensor index, chunk index) list of xmc_adam_step.  Tensors may start at any 4-byte
+ * ntensors entries, `chunks_dev` the (tensor index, chunk index) list of xmc_optim_step.  Tensors may start at any 4-byte
  * aligned address (16-byte accesses are taken only where every pointer of a chunk is 16-byte aligned) and have any length.
  * Rejected with XMC_EINVAL before anything is launched: NULL tables or counter, counts < 1, decay outside [0, 1), start < 0.
  *
@@ -595,18 +572,36 @@ typedef struct XmcEmaEntry {
 } XmcEmaEntry;
 int xmc_ema_step(const XmcEmaEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks, float decay, int start,
                  int32_t* num_updates_dev, const int32_t* skip_flag_dev, int bump, void* stream);
-/* xmc_adam_step / xmc_adam_step_scaled with the shadow update fused into the Adam update (the new weight is averaged while it
- * is in registers: 8 instead of 12 bytes of extra traffic per element).  `ema_table_dev` is parallel to `table_dev` (same
- * tensors, same order); only its `shadow` is read, NULL = that tensor has no shadow.  Weights, moments and step counters end up
- * bit-identical to those of the entry points above.  Under the loss scale, while the found-inf flag is up NOTHING moves:
- * weights, moments, step counters, shadow, *num_updates_dev. */
-int xmc_adam_ema_step(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors, const int32_t* chunks_dev,
-                      int nchunks, float lr, float beta1, float beta2, float eps, float grad_scale, float decay, int start,
-                      int32_t* num_updates_dev, int bump, void* stream);
-int xmc_adam_ema_step_scaled(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
-                             const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
-                             float* scale_dev, int32_t* flags_dev, int mode, float growth, float backoff, int interval,
-                             float decay, int start, int32_t* num_updates_dev, int bump, void* stream);
+/* One optimizer launch group: the Adam update of every tensor of `table`, optionally under the dynamic loss scale, optionally with
+ * the shadow update fused into it (the new weight is averaged while it is in registers: 8 instead of 12 bytes of extra traffic per
+ * element).  Weights, moments and step counters end up bit-identical with and without a shadow.
+ *   table, chunks, ntensors, nchunks: as described above (DEVICE arrays); required.
+ *   ema_table: NULL = no shadow (decay / start / num_updates_dev / bump are then ignored; num_updates_dev must be NULL too).  Else a
+ *              DEVICE array parallel to `table` (same tensors, same order); only its `shadow` is read, NULL = that tensor has
+ *              none.  decay, start, num_updates_dev as for xmc_ema_step; bump != 0: *num_updates_dev += 1 after the update.
+ *   scale_dev, flags_dev: both NULL = no loss scale: mode must be XMC_ADAM_UPDATE; growth / backoff / interval are ignored.  Both
+ *              set: the loss scale above; grad_scale must be 1 (the gradients are read times 1 / scale), interval >= 1 and mode
+ *              names at least one phase.  While the found-inf flag is up NOTHING moves: weights, moments, step counters, shadow,
+ *              *num_updates_dev.
+ * XMC_EINVAL, before anything is launched, for a NULL table or chunk list, counts < 1, one of scale_dev / flags_dev without the
+ * other, one of ema_table / num_updates_dev without the other, and what the lines above exclude. */
+typedef struct XmcOptimStep {
+    const XmcAdamEntry* table;
+    const XmcEmaEntry* ema_table;
+    const int32_t* chunks;
+    int32_t ntensors, nchunks;
+    float lr, beta1, beta2, eps, grad_scale;
+    float* scale_dev;
+    int32_t* flags_dev;
+    int32_t mode;             /* XMC_ADAM_* */
+    float growth, backoff;
+    int32_t interval;
+    float decay;
+    int32_t start;
+    int32_t* num_updates_dev;
+    int32_t bump;
+} XmcOptimStep;
+int xmc_optim_step(const XmcOptimStep* step /* host */, void* stream);
 
 /* ---- matching-aware gradient penalty, train_gan.py:241-247:  2 * mean_b ||[d logit / d img_b, d logit / d sent_b]||_2^6 ---------
  * ss[b] += sum_k x[b][k]^2 over an f32 block [B, cols] (cols % 4 == 0; ss zeroed by the caller, blocks accumulate);

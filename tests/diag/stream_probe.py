@@ -36,7 +36,7 @@ for (N, H, C) in ((512, 128, 64), (256, 256, 32), (256, 64, 128)):
     ms = timeit(lambda: L.call("xmc_affine2_act_fwd", p(dy), *[p(t) for t in ps], p(y), N, H * H, C, 0.2, L.BF16, st()))
     print(f"affine2_fwd    N{N} {H}x{H}x{C}: {ms*1e3:7.1f} us  {2*n*2/ms/1e9:5.2f} TB/s")
     red = torch.zeros(4, N, C, device="cuda")
-    ms = timeit(lambda: L.call("xmc_affine2_act_bwd", p(dy), p(ref), *[p(t) for t in ps], p(y), *[p(red[i]) for i in range(4)], N, H * H, C, 0.2, L.BF16, st()))
+    ms = timeit(lambda: L.call("xmc_affine2_act_bwd", p(dy), p(ref), *[p(t) for t in ps], p(y), *[p(red[i]) for i in range(4)], None, None, None, None, N, H, H, C, 0.2, L.BF16, st()))
     print(f"affine2_bwd    N{N} {H}x{H}x{C}: {ms*1e3:7.1f} us  {3*n*2/ms/1e9:5.2f} TB/s")
     ms = timeit(lambda: torch.add(dy, ref, out=g))
     print(f"torch add3     N{N} {H}x{H}x{C}: {ms*1e3:7.1f} us  {3*n*2/ms/1e9:5.2f} TB/s")

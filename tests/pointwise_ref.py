@@ -141,7 +141,7 @@ def affine_fwd_geom(N, H, W, C):
 
 
 def affine_bwd_geom(N, H, W, C, pool=False):
-    """xmc_affine2_act_bwd_dot_pool: loop units are pixels, or vertical pixel pairs when pooling; per-lane counts by walking the loops"""
+    """xmc_affine2_act_bwd: loop units are pixels, or vertical pixel pairs when pooling; per-lane counts by walking the loops"""
     C8 = C // 8
     HW = (H // 2) * W if pool else H * W
     g = affine_grid(HW, C8, N, 32 if pool else 64)

@@ -229,12 +229,12 @@ def test_header_binding_makefile_and_ops_agree_on_the_entry_point():
     assert 'xmc_note_kernel("caption_gather_kernel")' in src
 
 
-def test_the_abi_version_is_still_12():
+def test_the_abi_version_is_13():
     import xmc_gan_amd.lib as L
     hdr = open(os.path.join(ROOT, "include", "xmc_gan_hip.h")).read()
-    assert re.search(r"#define XMC_ABI_VERSION (\d+)", hdr).group(1) == "12" and L.ABI_VERSION == 12
+    assert re.search(r"#define XMC_ABI_VERSION (\d+)", hdr).group(1) == "13" and L.ABI_VERSION == 13
     for variant in ("bf16", "f16"):
-        assert L.load(variant).xmc_abi_version() == 12
+        assert L.load(variant).xmc_abi_version() == 13
 
 
 @pytest.mark.parametrize("variant", ["bf16", "f16"])

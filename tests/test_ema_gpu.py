@@ -489,7 +489,7 @@ def test_entry_point_updates_the_shadow_inside_the_replayed_graph(tmp_path):
 
 
 def test_entry_point_in_the_ieee_half_mode_counts_applied_generator_steps_only(tmp_path):
-    """the half mode's optimizer step runs under the dynamic loss scale (`xmc_adam_ema_step_scaled` inside the replayed graph): the
+    """the half mode's optimizer step runs under the dynamic loss scale (`xmc_optim_step` with the scale and the shadow table, inside the replayed graph): the
     average advances once per generator step the scaler did NOT skip"""
     import xmc_gan.train_gan as tg
     ops.reset_loss_scalers()

@@ -145,7 +145,7 @@ def test_geometry_model_constants_match_the_source():
     src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "xmc-gan_amd", "csrc", "pointwise.hip")).read()
     for text in ("constexpr int NT = 256;", "constexpr int UN = 4;", "constexpr int STREAM_BLOCKS = 1024;", "int cap = 256 * 16",
                  "nblocks(n8, NT, 512)", "nblocks(rows, groups * 8, 1024)", "nblocks(total, NT, 2048)", "affine_grid(HW, C / 8, N, g, ppb, 16)",
-                 "affine_grid(HW, C / 8, N, g, ppb, dx_pool ? 32 : 64)", "while (!wide && ppl > 4 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;",
+                 "affine_grid(HW, C / 8, N, g, ppb, dx_pool ? 32 : 64)", "while (ppl > 4 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;",
                  "if (HW >= 256 && out_dtype == XMC_F32 && C / 8 <= NT", "((int64_t)N * HW + 2047) / 2048", "if (ppb < 4 * groups) ppb = 4 * groups;"):
         assert text in src, text
 

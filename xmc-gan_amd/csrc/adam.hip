@@ -94,34 +94,6 @@ __global__ void adam_bump_kernel(const XmcAdamEntry* tab, int n, const int* __re
 
 extern "C" int xmc_adam_chunk_elems(void) { return CHUNK; }
 
-extern "C" int xmc_adam_step(const XmcAdamEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks,
-                             float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
-    if (!table_dev || !chunks_dev || ntensors < 1 || nchunks < 1) return XMC_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, reinterpret_cast<const int2*>(chunks_dev), lr, beta1, beta2, eps,
-                       grad_scale, (const float*)nullptr, (const int*)nullptr);
-    hipLaunchKernelGGL(adam_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)nullptr);
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int xmc_adam_step_scaled(const XmcAdamEntry* table_dev, int ntensors, const int32_t* chunks_dev, int nchunks,
-                                    float lr, float beta1, float beta2, float eps, float* scale_dev, int32_t* flags_dev,
-                                    int mode, float growth, float backoff, int interval, void* stream) {
-    if (!table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !scale_dev || !flags_dev || interval < 1 || (mode & 7) == 0) return XMC_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int2* ch = reinterpret_cast<const int2*>(chunks_dev);
-    if (mode & XMC_ADAM_CHECK) hipLaunchKernelGGL(adam_check_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ch, flags_dev);
-    if (mode & XMC_ADAM_UPDATE) {
-        hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ch, lr, beta1, beta2, eps, 1.f, (const float*)scale_dev,
-                           (const int*)flags_dev);
-        hipLaunchKernelGGL(adam_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)flags_dev);
-    }
-    if (mode & XMC_ADAM_RESCALE) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, scale_dev, flags_dev, growth, backoff, interval);
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Exponential moving average of the weights (the shadow set a GAN is sampled from at evaluation time), once per APPLIED
 // optimizer step:  e += (1 - d) * (p - e)  with d = 0 while fewer than `start` updates have been applied (then e = p, a bit-exact
@@ -251,38 +223,32 @@ extern "C" int xmc_ema_step(const XmcEmaEntry* table_dev, int ntensors, const in
     return 0;
 }
 
-extern "C" int xmc_adam_ema_step(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
-                                 const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
-                                 float grad_scale, float decay, int start, int32_t* num_updates_dev, int bump, void* stream) {
-    if (!table_dev || !ema_table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !ema_args_ok(decay, start, num_updates_dev))
-        return XMC_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ema_table_dev, reinterpret_cast<const int2*>(chunks_dev),
-                       lr, beta1, beta2, eps, grad_scale, (const float*)nullptr, (const int*)nullptr, decay, start,
-                       (const int*)num_updates_dev);
-    hipLaunchKernelGGL(ema_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)nullptr,
-                       (int*)num_updates_dev, bump);
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
 
-extern "C" int xmc_adam_ema_step_scaled(const XmcAdamEntry* table_dev, const XmcEmaEntry* ema_table_dev, int ntensors,
-                                        const int32_t* chunks_dev, int nchunks, float lr, float beta1, float beta2, float eps,
-                                        float* scale_dev, int32_t* flags_dev, int mode, float growth, float backoff, int interval,
-                                        float decay, int start, int32_t* num_updates_dev, int bump, void* stream) {
-    if (!table_dev || !ema_table_dev || !chunks_dev || ntensors < 1 || nchunks < 1 || !scale_dev || !flags_dev || interval < 1 ||
-        (mode & 7) == 0 || !ema_args_ok(decay, start, num_updates_dev))
+// One optimizer launch group.  The two optional parts are keyed on their pointers: a loss scale on scale_dev / flags_dev, a
+// shadow set on ema_table / num_updates_dev.  adam_kernel + adam_bump_kernel without a shadow, adam_ema_kernel + ema_bump_kernel
+// with one; the check in front and the rescale behind exist only under a loss scale.
+extern "C" int xmc_optim_step(const XmcOptimStep* s, void* stream) {
+    if (!s || !s->table || !s->chunks || s->ntensors < 1 || s->nchunks < 1) return XMC_EINVAL;
+    const bool scaled = s->scale_dev || s->flags_dev, shadow = s->ema_table || s->num_updates_dev;
+    if (scaled ? (!s->scale_dev || !s->flags_dev || s->interval < 1 || (s->mode & 7) == 0 || s->grad_scale != 1.f) : s->mode != XMC_ADAM_UPDATE)
         return XMC_EINVAL;
+    if (shadow && (!s->ema_table || !ema_args_ok(s->decay, s->start, s->num_updates_dev))) return XMC_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int2* ch = reinterpret_cast<const int2*>(chunks_dev);
-    if (mode & XMC_ADAM_CHECK) hipLaunchKernelGGL(adam_check_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ch, flags_dev);
-    if (mode & XMC_ADAM_UPDATE) {
-        hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(NT), 0, st, table_dev, ema_table_dev, ch, lr, beta1, beta2, eps, 1.f,
-                           (const float*)scale_dev, (const int*)flags_dev, decay, start, (const int*)num_updates_dev);
-        hipLaunchKernelGGL(ema_bump_kernel, dim3((ntensors + NT - 1) / NT), dim3(NT), 0, st, table_dev, ntensors, (const int*)flags_dev,
-                           (int*)num_updates_dev, bump);
+    const int2* ch = reinterpret_cast<const int2*>(s->chunks);
+    const float* sf = s->scale_dev;
+    const int* si = s->flags_dev;
+    const dim3 bump_grid((s->ntensors + NT - 1) / NT);
+    if (s->mode & XMC_ADAM_CHECK) hipLaunchKernelGGL(adam_check_kernel, dim3(s->nchunks), dim3(NT), 0, st, s->table, ch, s->flags_dev);
+    if ((s->mode & XMC_ADAM_UPDATE) && shadow) {
+        hipLaunchKernelGGL(adam_ema_kernel, dim3(s->nchunks), dim3(NT), 0, st, s->table, s->ema_table, ch, s->lr, s->beta1, s->beta2, s->eps,
+                           s->grad_scale, sf, si, s->decay, s->start, (const int*)s->num_updates_dev);
+        hipLaunchKernelGGL(ema_bump_kernel, bump_grid, dim3(NT), 0, st, s->table, s->ntensors, si, (int*)s->num_updates_dev, s->bump);
+    } else if (s->mode & XMC_ADAM_UPDATE) {
+        hipLaunchKernelGGL(adam_kernel, dim3(s->nchunks), dim3(NT), 0, st, s->table, ch, s->lr, s->beta1, s->beta2, s->eps, s->grad_scale, sf, si);
+        hipLaunchKernelGGL(adam_bump_kernel, bump_grid, dim3(NT), 0, st, s->table, s->ntensors, si);
     }
-    if (mode & XMC_ADAM_RESCALE) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, scale_dev, flags_dev, growth, backoff, interval);
+    if (s->mode & XMC_ADAM_RESCALE)
+        hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, s->scale_dev, s->flags_dev, s->growth, s->backoff, s->interval);
     XMC_LAUNCH_CHECK();
     return 0;
 }

@@ -426,9 +426,8 @@ static inline int gn_apply_blocks(int N, int HW, int C8) {
 // a 64-image batch that is ONE workgroup per image, 64 on a 256-CU chip, each walking its pixels in a serial loop (32x32x128: 7.6 us for
 // 17 MB) -- there 32 or 16 pixels per lane until the launch has a workgroup per CU
 static int gn_sums_blocks(int N, int HW, int groups) {
-    static const bool wide = xmc_debug_off("gn_sums_64");
     int ppl = 64;
-    while (!wide && ppl > 16 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;
+    while (ppl > 16 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;
     const int bx = (HW + groups * ppl - 1) / (groups * ppl);
     return bx < 1 ? 1 : bx;
 }
@@ -495,9 +494,9 @@ extern "C" int xmc_attn_pool_fwd(const void* key, const float* q, const void* x,
     XMC_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int xmc_attn_pool_bwd_acc(const void* key, const float* q, const void* x, const float* stats, const float* ctx,
-                                     const float* dctx, float* dq, void* dkey, void* dx, const void* dx_in, int N, int HW, int ncon,
-                                     int pk, int px, float scale, int dtype, void* s) {
+extern "C" int xmc_attn_pool_bwd(const void* key, const float* q, const void* x, const float* stats, const float* ctx,
+                                 const float* dctx, float* dq, void* dkey, void* dx, const void* dx_acc, int N, int HW, int ncon,
+                                 int pk, int px, float scale, int dtype, void* s) {
     if (!key || !q || !x || !stats || !ctx || !dctx || !dq || !dkey || !dx || N < 1 || HW < 1) return XMC_EINVAL;
     if (pk != AP_PK || px != AP_PX || ncon != AP_CON) return XMC_ESHAPE;
     if (xmc_zero_acc(dq, sizeof(float) * (size_t)N * AP_CON * AP_PK, ST(s)) != hipSuccess) return XMC_EINVAL;
@@ -505,14 +504,9 @@ extern "C" int xmc_attn_pool_bwd_acc(const void* key, const float* q, const void
     if (xmc_fixed_order()) ppc = (HW + AP_SLOTS - 1) / AP_SLOTS * AP_SLOTS;      // one run per image: dq gets one addition per element
     const int chunks = (HW + ppc - 1) / ppc;
     dim3 grid(chunks, N);
-    if (dtype == XMC_BF16) hipLaunchKernelGGL((attn_pool_bwd_kernel<XMC_BF16>), grid, dim3(NT), 0, ST(s), key, q, x, stats, ctx, dctx, dq, dkey, dx, dx_in, HW, scale, ppc);
-    else if (dtype == XMC_F32) hipLaunchKernelGGL((attn_pool_bwd_kernel<XMC_F32>), grid, dim3(NT), 0, ST(s), key, q, x, stats, ctx, dctx, dq, dkey, dx, dx_in, HW, scale, ppc);
+    if (dtype == XMC_BF16) hipLaunchKernelGGL((attn_pool_bwd_kernel<XMC_BF16>), grid, dim3(NT), 0, ST(s), key, q, x, stats, ctx, dctx, dq, dkey, dx, dx_acc, HW, scale, ppc);
+    else if (dtype == XMC_F32) hipLaunchKernelGGL((attn_pool_bwd_kernel<XMC_F32>), grid, dim3(NT), 0, ST(s), key, q, x, stats, ctx, dctx, dq, dkey, dx, dx_acc, HW, scale, ppc);
     else return XMC_EINVAL;
     XMC_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int xmc_attn_pool_bwd(const void* key, const float* q, const void* x, const float* stats, const float* ctx,
-                                 const float* dctx, float* dq, void* dkey, void* dx, int N, int HW, int ncon, int pk, int px,
-                                 float scale, int dtype, void* s) {
-    return xmc_attn_pool_bwd_acc(key, q, x, stats, ctx, dctx, dq, dkey, dx, nullptr, N, HW, ncon, pk, px, scale, dtype, s);
 }

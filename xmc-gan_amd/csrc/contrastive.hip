@@ -745,10 +745,10 @@ extern "C" int xmc_contrastive_bwd(const float* A, const float* B, const float* 
     if (e != hipSuccess) return -(1000 + (int)e);
     XmcConvDesc d;
     fill_linear_desc(d, w.Bh, nullptr, w.dST, n, D, w.n8, w.n32);
-    int rc = xmc_conv_wgrad(&d, w.dAh, stream);
+    int rc = xmc_conv_wgrad(&d, w.dAh, nullptr, stream);
     if (rc) return rc;
     fill_linear_desc(d, w.Ah, nullptr, w.dS, n, D, w.n8, w.n32);
-    rc = xmc_conv_wgrad(&d, w.dBh, stream);
+    rc = xmc_conv_wgrad(&d, w.dBh, nullptr, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(normalize_bwd_kernel, dim3(lb), dim3(NT), 0, st, w.Ah, w.dAh, w.ina, dA, n, D);
     hipLaunchKernelGGL(normalize_bwd_kernel, dim3(lb), dim3(NT), 0, st, w.Bh, w.dBh, w.inb, dB, n, D);

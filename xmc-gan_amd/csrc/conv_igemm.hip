@@ -395,7 +395,6 @@ int launch(const XmcConvDesc& d, hipStream_t st) {
 
 template <int DT>
 int dispatch(const XmcConvDesc& d, hipStream_t st) {
-    static const int variant = xmc_debug_off("igemm128") ? 1 : 0;
     // batch-sized GEMMs (the conditioning MLPs: M = batch, K = N = 256): a 128-wide N tile leaves 4 workgroups on the
     // chip and each walks all of K alone; 32-wide tiles give 4x the workgroups and a 4x shorter critical path
     static const bool no_small = xmc_debug_off("no_small_m");
@@ -408,7 +407,6 @@ int dispatch(const XmcConvDesc& d, hipStream_t st) {
     if (!no_small && (int64_t)d.N * d.MH * d.MW <= 1024) return launch<DT, 128, 32, 4, 1, 2>(d, st);
     if (d.CDw % 128 == 0) {
         const int64_t M = (int64_t)d.N * d.MH * d.MW;
-        if (variant == 1) return launch<DT, 128, 128, 2, 2, 2>(d, st);
         // 256x128 tile, each wave a 128x64 patch: 1.33x fewer LDS fragment bytes per MFMA than 64x64 patches (the
         // 128x128 structure measures 600-650 TF/s against a no-global-load ceiling of ~800 TF/s: LDS-read bound)
         // 256x256 tile, 8 waves of the same 128x64 patches: the A rows are shared by twice as many columns, 32 KB instead of

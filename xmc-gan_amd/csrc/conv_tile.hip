@@ -1078,9 +1078,8 @@ int launch_ptile(const XmcConvDesc& d, const TileCfg& t, hipStream_t st) {
         }
     }
     static const bool no_m32 = xmc_debug_off("no_ptile_m32");
-    static const bool m32_all = xmc_debug_off("ptile_m32_all");
     if (!no_m32 && d.ntaps == 9 && d.out_dtype == XMC_BF16 && t.slab == 64 &&
-        (m32_all || d.res || d.dst2 || d.dst_pool || d.mask || d.sign_bits)) {      // one matrix wave per SIMD: 32x32x16 form
+        (d.res || d.dst2 || d.dst_pool || d.mask || d.sign_bits)) {      // one matrix wave per SIMD: 32x32x16 form
         // the epilogue option sets of the training step as compile-time instantiations (kEpi*), anything else through the
         // descriptor-reading one
         int epi = xmc_epi_mask(d);

@@ -10,8 +10,6 @@
 // (train_gan.py:228,251,288) for every conv2d / Linear on the path.
 #include "common.h"
 
-extern "C" int xmc_conv_wgrad_bias(const XmcConvDesc* d, float* dwp, float* dbias, void* stream);
-
 namespace {
 
 
@@ -233,10 +231,8 @@ int xmc_conv_wgrad_tile_try(const XmcConvDesc* d, float* dwp, float* dbias, void
 int xmc_conv_wgrad_row_try(const XmcConvDesc* d, float* dwp, float* dbias, void* stream);    // conv_wgrad_row.hip
 int xmc_conv_wgrad_up_try(const XmcConvDesc* d, float* dwp, float* dbias, void* stream);     // conv_wgrad_up.hip
 
-extern "C" int xmc_conv_wgrad(const XmcConvDesc* d, float* dwp, void* stream) { return xmc_conv_wgrad_bias(d, dwp, nullptr, stream); }
-
-// same, and additionally dbias[co] += sum over all pixels of dy[.,co] (f32 [CD], zeroed by the caller) when dbias != NULL
-extern "C" int xmc_conv_wgrad_bias(const XmcConvDesc* d, float* dwp, float* dbias, void* stream) {
+// dbias != NULL: additionally dbias[co] += sum over all pixels of dy[.,co] (f32 [XMC_BIAS_REPLICAS][CD], zeroed by the caller)
+extern "C" int xmc_conv_wgrad(const XmcConvDesc* d, float* dwp, float* dbias, void* stream) {
     if (!d || !d->src || !d->dst || !dwp) return XMC_EINVAL;
     if (d->dtype != XMC_BF16 && d->dtype != XMC_F32) return XMC_EINVAL;
     const int esz = xmc_esz(d->dtype);

@@ -543,9 +543,9 @@ int plan(const XmcConvDesc* d, WtCfg* t, int* mode, int* tn) {
     return 1;
 }
 
-template <int NTAPS, int MODE, int TN, int CW>
+template <int NTAPS, int MODE, int TN>
 int launch(const XmcConvDesc& d, const WtCfg& t, hipStream_t st) {
-    constexpr int BN = 16 * TN;
+    constexpr int BN = 16 * TN, CW = 8;           // eight compute waves: two per SIMD
     const size_t lds = (size_t)3 * BN * 128 + 2 * (size_t)t.patch_bytes;
     if (lds > XMC_MAX_DYN_LDS) return XMC_ESHAPE;
     const int ntiles = d.N * t.tiles_y * t.tiles_x, ny = d.CDw / BN;
@@ -553,9 +553,9 @@ int launch(const XmcConvDesc& d, const WtCfg& t, hipStream_t st) {
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
     gx = xmc_ab_grid(gx);
-    // epilogue option sets of the training step as compile-time instantiations (common.h: kEpi*), eight compute waves only
+    // epilogue option sets of the training step as compile-time instantiations (common.h: kEpi*)
     static const bool no_epi = xmc_debug_off("no_wtile_epi");
-    const int epi = (no_epi || CW != 8) ? -1 : xmc_epi_mask(d);
+    const int epi = no_epi ? -1 : xmc_epi_mask(d);
 #define XMC_W2_EPI(E)                                                                                                                          \
     if (epi == (E)) {                                                                                                                          \
         XMC_ALLOW_BIG_LDS((wtile2_kernel<NTAPS, MODE, TN, CW, (E)>));                                                                          \
@@ -565,20 +565,20 @@ int launch(const XmcConvDesc& d, const WtCfg& t, hipStream_t st) {
         XMC_LAUNCH_CHECK();                                                                                                                    \
         return 0;                                                                                                                              \
     }
-    if constexpr (CW == 8 && NTAPS == 9 && TN == 8) {
+    if constexpr (NTAPS == 9 && TN == 8) {
         XMC_W2_EPI(kEpiGSum) XMC_W2_EPI(kEpiDKeep) XMC_W2_EPI(kEpiDFwd) XMC_W2_EPI(kEpiDLast) XMC_W2_EPI(kEpiMask) XMC_W2_EPI(0) XMC_W2_EPI(kEpiDLin)
         XMC_W2_EPI(kEpiDKeepS) XMC_W2_EPI(kEpiDLastS) XMC_W2_EPI(kEpiDgDot)
         XMC_W2_EPI(kEpiBias) XMC_W2_EPI(kEpiBias | kEpiLrelu)            // the attention-modulation blocks' convolutions
-    } else if constexpr (CW == 8 && NTAPS == 9) {
+    } else if constexpr (NTAPS == 9) {
         XMC_W2_EPI(kEpiBias) XMC_W2_EPI(kEpiBias | kEpiLrelu) XMC_W2_EPI(0)
-    } else if constexpr (CW == 8 && MODE == 1 && TN == 8) {
+    } else if constexpr (MODE == 1 && TN == 8) {
         XMC_W2_EPI(kEpiLrelu) XMC_W2_EPI(0) XMC_W2_EPI(kEpiMask)
-    } else if constexpr (CW == 8 && NTAPS == 4 && MODE == 0) {
+    } else if constexpr (NTAPS == 4 && MODE == 0) {
         XMC_W2_EPI(kEpiRes) XMC_W2_EPI(kEpiBias) XMC_W2_EPI(0)
     }
 #undef XMC_W2_EPI
     if (d.sign_bits || d.dot) return 1;          // only the compile-time sets above carry these two; the next kernel in line takes it
-    xmc_note_generic_epi(NTAPS == 9 ? (TN == 8 ? "wtile2<9,0,8>" : "wtile2<9,0,4>") : MODE == 1 ? (TN == 8 ? "wtile2<4,1,8>" : "wtile2<4,1,4>") : "wtile2<4,0>", CW == 8 ? xmc_epi_mask(d) : -1);
+    xmc_note_generic_epi(NTAPS == 9 ? (TN == 8 ? "wtile2<9,0,8>" : "wtile2<9,0,4>") : MODE == 1 ? (TN == 8 ? "wtile2<4,1,8>" : "wtile2<4,1,4>") : "wtile2<4,0>", xmc_epi_mask(d));
     XMC_ALLOW_BIG_LDS((wtile2_kernel<NTAPS, MODE, TN, CW>));
     hipLaunchKernelGGL((wtile2_kernel<NTAPS, MODE, TN, CW>), dim3((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), dim3(64 * CW + 256), lds, st, d, t,
                        ntiles);
@@ -596,11 +596,8 @@ int xmc_conv_wtile_try(const XmcConvDesc* d, void* stream) {
     if (!plan(d, &t, &mode, &tn)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
-    static const bool cw4 = xmc_debug_off("wtile_cw4");      // A/B: one compute wave per SIMD
-#define WT_GO(NT_, MD_, TN_) (cw4 ? launch<NT_, MD_, TN_, 4>(*d, t, st) : launch<NT_, MD_, TN_, 8>(*d, t, st))
-    if (mode == 1) rc = tn == 8 ? WT_GO(4, 1, 8) : WT_GO(4, 1, 4);
-    else if (d->ntaps == 9) rc = tn == 8 ? WT_GO(9, 0, 8) : WT_GO(9, 0, 4);
-    else rc = tn == 8 ? WT_GO(4, 0, 8) : WT_GO(4, 0, 4);
-#undef WT_GO
+    if (mode == 1) rc = tn == 8 ? launch<4, 1, 8>(*d, t, st) : launch<4, 1, 4>(*d, t, st);
+    else if (d->ntaps == 9) rc = tn == 8 ? launch<9, 0, 8>(*d, t, st) : launch<9, 0, 4>(*d, t, st);
+    else rc = tn == 8 ? launch<4, 0, 8>(*d, t, st) : launch<4, 0, 4>(*d, t, st);
     return rc == XMC_ESHAPE ? 1 : rc;
 }

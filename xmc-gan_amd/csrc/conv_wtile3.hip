@@ -640,10 +640,6 @@ int xmc_conv_wtile3_try(const XmcConvDesc* d, void* stream) {
     W3Cfg t;
     int mode = 0, wm = 2;
     if (!plan3(d, &t, &mode, &wm)) return 1;
-    // BN = 128 (64 x 64 wave tiles: the same fragment-read load as the role-split kernel, without its dedicated staging waves) measures
-    // 3-6 % behind conv_wtile.hip on the 128-channel layers: kept for A/B runs only
-    static const bool bn128 = xmc_debug_off("wtile3_bn128"), bn128_epi = xmc_debug_off("wtile3_bn128_epi"), bn128_plain = xmc_debug_off("wtile3_bn128_plain");
-    const bool heavy = d->res || d->dst2 || d->dst_pool || d->mask || d->sign_bits;
     static const bool any_count = xmc_debug_off("wtile3_any_tile_count");      // tests: small batches through this kernel
     const long long tiles = (long long)d->N / t.ipt * t.tiles_y * t.tiles_x * d->nclass;
     if (t.ipt > 1) {
@@ -652,7 +648,9 @@ int xmc_conv_wtile3_try(const XmcConvDesc* d, void* stream) {
         if (wm == 2 && tiles * (d->CDw / 256) < 256 && !any_count) wm = 4;
         if (wm == 4 && tiles * (d->CDw / 128) < 256 && !any_count) return 1;
     } else {
-        if (wm == 4 && !(bn128 || (bn128_epi && heavy) || (bn128_plain && !heavy))) return 1;
+        // BN = 128 (64 x 64 wave tiles: the same fragment-read load as the role-split kernel, without its dedicated staging waves) measures
+        // 3-6 % behind conv_wtile.hip on the 128-channel layers
+        if (wm == 4) return 1;
         // 256-channel tiles halve the number of workgroups: below one tile per CU the role-split kernel (128-channel tiles, twice the
         // workgroups) wins -- 128x128 / batch 64: 10.8 vs 10.4 ms per iteration
         if (wm == 2 && tiles * (d->CDw / 256) < 256 && !any_count) return 1;

@@ -505,66 +505,12 @@ __global__ void hinge_bwd_kernel(const void* x, int stride, float sign, const fl
 }
 
 // ------------------------------------------------------------------ weight pack / unpack
-// value of packed element i of [KHW][rows_pad][cols_pad].  groups > 1: w is a grouped-convolution weight [Co][Ci/groups][KHW];
-// the packed matrix is its block-diagonal expansion
-__device__ __forceinline__ float pack_value(const float* __restrict__ w, int Co, int Ci, int KHW, int rows_pad, int cols_pad,
-                                            int transpose, const int32_t* __restrict__ row_perm, int groups, int64_t i) {
-    const int cog = Co / groups, cig = Ci / groups;
-    int c = (int)(i % cols_pad);
-    int64_t q = i / cols_pad;
-    int r = (int)(q % rows_pad);
-    int t = (int)(q / rows_pad);
-    int co = transpose ? c : r, ci = transpose ? r : c;
-    float v = 0.f;
-    if (co < Co && ci < Ci) {
-        int sco = row_perm ? row_perm[co] : co;
-        if (groups == 1) v = w[((int64_t)sco * Ci + ci) * KHW + t];
-        else if (sco / cog == ci / cig) v = w[((int64_t)sco * cig + ci % cig) * KHW + t];
-    }
-    return v;
-}
-// Fused nearest-x2 upsample + 3x3 convolution: output parity class (i,j) sees only a 2x2 neighbourhood of the
+// groups > 1: w is a grouped-convolution weight [Co][Ci/groups][KHW]; the packed matrix [KHW][rows_pad][cols_pad] is its
+// block-diagonal expansion.
+// Fused nearest-x2 upsample + 3x3 convolution (XmcPackJob.upconv): output parity class (i,j) sees only a 2x2 neighbourhood of the
 // low-resolution input, with weights that are sums of the 3x3 taps landing on the same low-res pixel:
 //   rows: i=0: {kh=0} | {kh=1,2}     i=1: {kh=0,1} | {kh=2}        (same for columns)
 // slice index = (i*2+j)*4 + th*2+tw.  Summation in f32, one rounding to the kernel dtype.
-__device__ __forceinline__ float pack_upconv_value(const float* __restrict__ w, int Co, int Ci, int rows_pad, int cols_pad,
-                                                   int transpose, int64_t idx) {
-    int c = (int)(idx % cols_pad);
-    int64_t q = idx / cols_pad;
-    int r = (int)(q % rows_pad);
-    int sl = (int)(q / rows_pad);
-    int cls = sl >> 2, t = sl & 3;
-    int i = cls >> 1, j = cls & 1, th = t >> 1, tw = t & 1;
-    int co = transpose ? c : r, ci = transpose ? r : c;
-    float v = 0.f;
-    if (co < Co && ci < Ci) {
-        int kh0 = (i == 0) ? (th == 0 ? 0 : 1) : (th == 0 ? 0 : 2), kh1 = (i == 0) ? (th == 0 ? 0 : 2) : (th == 0 ? 1 : 2);
-        int kw0 = (j == 0) ? (tw == 0 ? 0 : 1) : (tw == 0 ? 0 : 2), kw1 = (j == 0) ? (tw == 0 ? 0 : 2) : (tw == 0 ? 1 : 2);
-        const float* wp = w + ((int64_t)co * Ci + ci) * 9;
-        for (int kh = kh0; kh <= kh1; ++kh)
-            for (int kw = kw0; kw <= kw1; ++kw) v += wp[kh * 3 + kw];
-    }
-    return v;
-}
-template <int DT>
-__global__ void pack_weight_kernel(const float* w, void* wpk, int Co, int Ci, int KHW, int rows_pad, int cols_pad,
-                                   int transpose, const int32_t* row_perm, int groups) {
-    const int64_t total = (int64_t)KHW * rows_pad * cols_pad;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = pack_value(w, Co, Ci, KHW, rows_pad, cols_pad, transpose, row_perm, groups, i);
-        if (DT == XMC_BF16) reinterpret_cast<xmc_h16*>(wpk)[i] = (xmc_h16)v;
-        else reinterpret_cast<float*>(wpk)[i] = v;
-    }
-}
-template <int DT>
-__global__ void pack_upconv_kernel(const float* w, void* wpk, int Co, int Ci, int rows_pad, int cols_pad, int transpose) {
-    const int64_t total = (int64_t)16 * rows_pad * cols_pad;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const float v = pack_upconv_value(w, Co, Ci, rows_pad, cols_pad, transpose, idx);
-        if (DT == XMC_BF16) reinterpret_cast<xmc_h16*>(wpk)[idx] = (xmc_h16)v;
-        else reinterpret_cast<float*>(wpk)[idx] = v;
-    }
-}
 // All packed copies of a network's weights in one launch (after the optimizer step that changed them).  The job table travels
 // in the kernel arguments (capturable, no device-side table).  Work is cut into chunks of PM_CHUNK (row, column) positions of
 // the packed matrix; first[j] = first chunk of job j, so blocks are dealt in proportion to the size of a job.  A thread owns one
@@ -917,7 +863,7 @@ extern "C" int xmc_colsum(const void* x, float* out, int64_t rows, int C, int dt
     XMC_LAUNCH_CHECK();
     return 0;
 }
-static int pool2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* s) {
+extern "C" int xmc_sumpool2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* s) {
     if (C % 8 || H % 2 || W % 2) return XMC_EALIGN;
     int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
     dim3 g(nblocks(total)), blk(NT);
@@ -926,12 +872,6 @@ static int pool2(const void* x, void* y, int N, int H, int W, int C, float scale
     else return XMC_EINVAL;
     XMC_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int xmc_avgpool2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* s) {
-    return pool2(x, y, N, H, W, C, 0.25f, dtype, s);
-}
-extern "C" int xmc_sumpool2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* s) {
-    return pool2(x, y, N, H, W, C, scale, dtype, s);
 }
 extern "C" int xmc_upsample2(const void* x, void* y, int N, int H, int W, int C, float scale, int dtype, void* s) {
     if (C % 8) return XMC_EALIGN;
@@ -999,8 +939,7 @@ static inline int affine_grid(int HW, int C8, int N, dim3& g, int& ppb, int ppl)
     const int groups = NT / C8;
     // small maps of a small batch (64 images of 32x32: one workgroup per image, 32 dependent load-compute-store rounds each -- 25 us for
     // 50 MB): fewer pixels per lane until the launch has a workgroup per CU
-    static const bool wide = xmc_debug_off("affine_wide");
-    while (!wide && ppl > 4 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;
+    while (ppl > 4 && (long long)N * ((HW + groups * ppl - 1) / (groups * ppl)) < 256) ppl >>= 1;
     int per = groups * ppl;
     int bx = (HW + per - 1) / per;
     if (bx < 1) bx = 1;
@@ -1019,10 +958,10 @@ extern "C" int xmc_affine2_act_fwd(const void* x, const float* g0, const float* 
     XMC_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int xmc_affine2_act_bwd_dot_pool(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                            const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                                            const void* dx_in, const float* alpha_dev, float* dot, void* dx_pool, int N, int H, int W,
-                                            int C, float slope, int dtype, void* s) {
+extern "C" int xmc_affine2_act_bwd(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
+                                   const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
+                                   const void* dx_in, const float* alpha_dev, float* dot, void* dx_pool, int N, int H, int W,
+                                   int C, float slope, int dtype, void* s) {
     if (C % 8 || C / 8 > NT) return XMC_EALIGN;
     if ((alpha_dev == nullptr) != (dot == nullptr)) return XMC_EINVAL;
     const int C8 = C / 8;
@@ -1043,31 +982,6 @@ extern "C" int xmc_affine2_act_bwd_dot_pool(const void* x, const void* dy, const
     XMC_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int xmc_affine2_act_bwd_dot(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                       const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                                       const void* dx_in, const float* alpha_dev, float* dot, int N, int HW, int C, float slope,
-                                       int dtype, void* s) {
-    return xmc_affine2_act_bwd_dot_pool(x, dy, g0, b0, g1, b1, dx, dg0, db0, dg1, db1, dx_in, alpha_dev, dot, nullptr, N, 1, HW, C, slope, dtype, s);
-}
-extern "C" int xmc_affine2_act_bwd_acc(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                       const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                                       const void* dx_in, int N, int HW, int C, float slope, int dtype, void* s) {
-    return xmc_affine2_act_bwd_dot(x, dy, g0, b0, g1, b1, dx, dg0, db0, dg1, db1, dx_in, nullptr, nullptr, N, HW, C, slope, dtype, s);
-}
-extern "C" int xmc_affine2_act_bwd(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                   const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                                   int N, int HW, int C, float slope, int dtype, void* s) {
-    return xmc_affine2_act_bwd_acc(x, dy, g0, b0, g1, b1, dx, dg0, db0, dg1, db1, nullptr, N, HW, C, slope, dtype, s);
-}
-extern "C" int xmc_affine2_lrelu_fwd(const void* x, const float* g0, const float* b0, const float* g1, const float* b1,
-                                     void* y, int N, int HW, int C, int dtype, void* s) {
-    return xmc_affine2_act_fwd(x, g0, b0, g1, b1, y, N, HW, C, XMC_LRELU, dtype, s);
-}
-extern "C" int xmc_affine2_lrelu_bwd(const void* x, const void* dy, const float* g0, const float* b0, const float* g1,
-                                     const float* b1, void* dx, float* dg0, float* db0, float* dg1, float* db1,
-                                     int N, int HW, int C, int dtype, void* s) {
-    return xmc_affine2_act_bwd(x, dy, g0, b0, g1, b1, dx, dg0, db0, dg1, db1, N, HW, C, XMC_LRELU, dtype, s);
-}
 extern "C" int xmc_hinge_fwd(const void* x, int stride, float sign, float* out, int64_t n, int dtype, void* s) {
     if (n < 1 || stride < 1) return XMC_ESHAPE;
     if (dtype == XMC_BF16) hipLaunchKernelGGL((hinge_fwd_kernel<XMC_BF16>), dim3(1), dim3(NT), 0, ST(s), x, stride, sign, out, n);
@@ -1081,20 +995,6 @@ extern "C" int xmc_hinge_bwd(const void* x, int stride, float sign, const float*
     dim3 g(nblocks(n)), blk(NT);
     if (dtype == XMC_BF16) hipLaunchKernelGGL((hinge_bwd_kernel<XMC_BF16>), g, blk, 0, ST(s), x, stride, sign, dloss, dx, n);
     else if (dtype == XMC_F32) hipLaunchKernelGGL((hinge_bwd_kernel<XMC_F32>), g, blk, 0, ST(s), x, stride, sign, dloss, dx, n);
-    else return XMC_EINVAL;
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int xmc_pack_weight_grouped(const float* w, void* wpk, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                                       int transpose, int dtype, const int32_t* row_perm, int groups, void* s) {
-    if (!w || !wpk || groups < 1 || Co % groups || Ci % groups) return XMC_EINVAL;
-    if (transpose ? (rows_pad < Ci || cols_pad < Co) : (rows_pad < Co || cols_pad < Ci)) return XMC_ESHAPE;
-    int64_t total = (int64_t)KH * KW * rows_pad * cols_pad;
-    dim3 g(nblocks(total)), blk(NT);
-    if (dtype == XMC_BF16)
-        hipLaunchKernelGGL((pack_weight_kernel<XMC_BF16>), g, blk, 0, ST(s), w, wpk, Co, Ci, KH * KW, rows_pad, cols_pad, transpose, row_perm, groups);
-    else if (dtype == XMC_F32)
-        hipLaunchKernelGGL((pack_weight_kernel<XMC_F32>), g, blk, 0, ST(s), w, wpk, Co, Ci, KH * KW, rows_pad, cols_pad, transpose, row_perm, groups);
     else return XMC_EINVAL;
     XMC_LAUNCH_CHECK();
     return 0;
@@ -1123,50 +1023,16 @@ extern "C" int xmc_pack_weight_multi(const XmcPackJob* jobs, int njobs, void* s)
     }
     return 0;
 }
-extern "C" int xmc_pack_weight(const float* w, void* wpk, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                               int transpose, int dtype, const int32_t* row_perm, void* s) {
-    return xmc_pack_weight_grouped(w, wpk, Co, Ci, KH, KW, rows_pad, cols_pad, transpose, dtype, row_perm, 1, s);
-}
-extern "C" int xmc_unpack_wgrad_grouped(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                                        const float* scale_dev, const int32_t* row_perm, int accumulate, int groups, void* s) {
+extern "C" int xmc_unpack_wgrad(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
+                                const float* scale_dev, const int32_t* row_perm, int accumulate, int groups,
+                                const float* gb_replicas, float* gb, int CD, const float* bias_dot, float* dot, void* s) {
     if (!dwp || !gw || rows_pad < Co || cols_pad < Ci || groups < 1 || Co % groups || Ci % groups) return XMC_EINVAL;
+    const bool bias = gb_replicas || gb;
+    if (bias && (!gb_replicas || !gb || CD < 1 || groups != 1)) return XMC_EINVAL;
+    if ((bias_dot == nullptr) != (dot == nullptr) || (bias_dot && (row_perm || !bias))) return XMC_EINVAL;
     int64_t total = (int64_t)Co * (Ci / groups) * KH * KW;
     hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(nblocks(total)), dim3(NT), 0, ST(s), dwp, gw, Co, Ci, KH * KW, rows_pad, cols_pad,
-                       scale_dev, row_perm, accumulate, (const float*)nullptr, (float*)nullptr, 0, groups, (const float*)nullptr, (float*)nullptr);
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int xmc_unpack_wgrad(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                                const float* scale_dev, const int32_t* row_perm, int accumulate, void* s) {
-    return xmc_unpack_wgrad_grouped(dwp, gw, Co, Ci, KH, KW, rows_pad, cols_pad, scale_dev, row_perm, accumulate, 1, s);
-}
-extern "C" int xmc_unpack_wgrad_bias_dot(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                                         const float* scale_dev, const int32_t* row_perm, int accumulate,
-                                         const float* gb_replicas, float* gb, int CD, const float* bias_dot, float* dot, void* s) {
-    if (!dwp || !gw || rows_pad < Co || cols_pad < Ci || !gb_replicas || !gb || CD < 1) return XMC_EINVAL;
-    if ((bias_dot == nullptr) != (dot == nullptr) || (bias_dot && row_perm)) return XMC_EINVAL;
-    int64_t total = (int64_t)Co * Ci * KH * KW;
-    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(nblocks(total)), dim3(NT), 0, ST(s), dwp, gw, Co, Ci, KH * KW, rows_pad, cols_pad,
-                       scale_dev, row_perm, accumulate, gb_replicas, gb, CD, 1, bias_dot, dot);
-    XMC_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int xmc_unpack_wgrad_bias(const float* dwp, float* gw, int Co, int Ci, int KH, int KW, int rows_pad, int cols_pad,
-                                     const float* scale_dev, const int32_t* row_perm, int accumulate,
-                                     const float* gb_replicas, float* gb, int CD, void* s) {
-    return xmc_unpack_wgrad_bias_dot(dwp, gw, Co, Ci, KH, KW, rows_pad, cols_pad, scale_dev, row_perm, accumulate, gb_replicas, gb, CD,
-                                     nullptr, nullptr, s);
-}
-
-extern "C" int xmc_pack_weight_upconv(const float* w, void* wpk, int Co, int Ci, int rows_pad, int cols_pad, int transpose,
-                                      int dtype, void* s) {
-    if (!w || !wpk) return XMC_EINVAL;
-    if (transpose ? (rows_pad < Ci || cols_pad < Co) : (rows_pad < Co || cols_pad < Ci)) return XMC_ESHAPE;
-    int64_t total = (int64_t)16 * rows_pad * cols_pad;
-    dim3 g(nblocks(total)), blk(NT);
-    if (dtype == XMC_BF16) hipLaunchKernelGGL((pack_upconv_kernel<XMC_BF16>), g, blk, 0, ST(s), w, wpk, Co, Ci, rows_pad, cols_pad, transpose);
-    else if (dtype == XMC_F32) hipLaunchKernelGGL((pack_upconv_kernel<XMC_F32>), g, blk, 0, ST(s), w, wpk, Co, Ci, rows_pad, cols_pad, transpose);
-    else return XMC_EINVAL;
+                       scale_dev, row_perm, accumulate, gb_replicas, gb, bias ? CD : 0, groups, bias_dot, dot);
     XMC_LAUNCH_CHECK();
     return 0;
 }

@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("XMC_LIB_PATH", os.path.join(HERE, "libxmc_gan_hip.so"))   # override: kernel experiments
 LIB_PATH_F16 = os.environ.get("XMC_LIB_PATH_F16", os.path.join(HERE, "libxmc_gan_hip_f16.so"))
-ABI_VERSION = 12          # include/xmc_gan_hip.h XMC_ABI_VERSION; the ctypes structures below mirror that version
+ABI_VERSION = 13          # include/xmc_gan_hip.h XMC_ABI_VERSION; the ctypes structures below mirror that version
 
 # BF16 is the dtype code of "the 16-bit storage format of the loaded build": bf16 in libxmc_gan_hip.so, IEEE half in
 # libxmc_gan_hip_f16.so (the same sources compiled with -DXMC_H16_IS_F16; `use_variant`)
@@ -57,6 +57,16 @@ class EmaEntry(C.Structure):
     _fields_ = [("shadow", vp), ("param", vp), ("n", i64)]
 
 
+class OptimStep(C.Structure):
+    _fields_ = [("table", vp), ("ema_table", vp), ("chunks", vp), ("ntensors", i32), ("nchunks", i32),
+                ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("grad_scale", f32),
+                ("scale_dev", vp), ("flags_dev", vp), ("mode", i32), ("growth", f32), ("backoff", f32), ("interval", i32),
+                ("decay", f32), ("start", i32), ("num_updates_dev", vp), ("bump", i32)]
+
+
+ADAM_CHECK, ADAM_UPDATE, ADAM_RESCALE = 1, 2, 4      # XmcOptimStep.mode
+
+
 # name -> argtypes  (restype is int unless listed in _RESTYPE)
 _SIGS = {
     "xmc_abi_version": [],
@@ -66,17 +76,10 @@ _SIGS = {
     "xmc_set_prezeroed": [i32],
     "xmc_conv_splitk_ws_bytes": [vp],
     "xmc_conv_igemm": [C.POINTER(ConvDesc), vp],
-    "xmc_conv_wgrad": [C.POINTER(ConvDesc), vp, vp],
-    "xmc_conv_wgrad_bias": [C.POINTER(ConvDesc), vp, vp, vp],
-    "xmc_pack_weight": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
-    "xmc_pack_weight_grouped": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp],
-    "xmc_pack_weight_upconv": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "xmc_conv_wgrad": [C.POINTER(ConvDesc), vp, vp, vp],
     "xmc_pack_weight_multi": [C.POINTER(PackJob), i32, vp],
     "xmc_axpby_up": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-    "xmc_unpack_wgrad": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
-    "xmc_unpack_wgrad_grouped": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],
-    "xmc_unpack_wgrad_bias": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp],
-    "xmc_unpack_wgrad_bias_dot": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp],
+    "xmc_unpack_wgrad": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp],
     "xmc_nchw_to_nhwc8": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_nhwc8_to_nchw": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_lrelu": [vp, vp, i64, f32, i32, vp],
@@ -110,24 +113,17 @@ _SIGS = {
     "xmc_spectral_sigma": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "xmc_spectral_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "xmc_colsum": [vp, vp, i64, i32, i32, vp],
-    "xmc_avgpool2": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_upsample2": [vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "xmc_sumpool2": [vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "xmc_global_avgpool": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_global_avgpool_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_affine2_act_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
-    "xmc_affine2_act_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
-    "xmc_affine2_act_bwd_acc": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
-    "xmc_affine2_act_bwd_dot": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
-    "xmc_affine2_act_bwd_dot_pool": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
-    "xmc_affine2_lrelu_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-    "xmc_affine2_lrelu_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "xmc_affine2_act_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "xmc_groupnorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp],
     "xmc_groupnorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "xmc_attn_pool_ws_floats": [i32, i32],
     "xmc_attn_pool_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp],
-    "xmc_attn_pool_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp],
-    "xmc_attn_pool_bwd_acc": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp],
+    "xmc_attn_pool_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp],
     "xmc_word_pool_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "xmc_word_pool_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "xmc_gvec_fwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -160,11 +156,8 @@ _SIGS = {
     "xmc_gp_finish": [vp, i32, vp, vp, f32, vp],
     "xmc_rows_scale": [vp, vp, vp, vp, i32, i64, vp],
     "xmc_adam_chunk_elems": [],
-    "xmc_adam_step": [vp, i32, vp, i32, f32, f32, f32, f32, f32, vp],
-    "xmc_adam_step_scaled": [vp, i32, vp, i32, f32, f32, f32, f32, vp, vp, i32, f32, f32, i32, vp],
+    "xmc_optim_step": [C.POINTER(OptimStep), vp],
     "xmc_ema_step": [vp, i32, vp, i32, f32, i32, vp, vp, i32, vp],
-    "xmc_adam_ema_step": [vp, vp, i32, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp, i32, vp],
-    "xmc_adam_ema_step_scaled": [vp, vp, i32, vp, i32, f32, f32, f32, f32, vp, vp, i32, f32, f32, i32, f32, i32, vp, i32, vp],
     "xmc_dstem_compose": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "xmc_dstem_compose_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "xmc_dstem_pack": [vp, vp, vp],

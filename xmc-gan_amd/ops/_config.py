@@ -69,7 +69,7 @@ GP_INNER_SCALE_F16 = float(os.environ.get("XMC_GP_INNER_SCALE", 256.0))
 
 class LossScaler:
     """device-resident dynamic loss scale: ``sf`` = [scale, 1/scale] (f32), ``si`` = [found-inf flag of the running step, finite
-    steps in a row, the flag at the last finished step, steps skipped so far] (int32); updated by `xmc_adam_step_scaled`."""
+    steps in a row, the flag at the last finished step, steps skipped so far] (int32); updated by `xmc_optim_step`."""
 
     def __init__(self, device, init=None, growth=2.0, backoff=0.5, interval=None):
         init = LOSS_SCALE_F16 if init is None else float(init)

@@ -658,7 +658,7 @@ def _pooled_take(dz):
 
 def _conv_wgrad_raw(x, dy, geom, scale=None, up=False, want_bias=False, bias_dot=None, dot=None):
     """gw [Co,Ci,k,k] f32 from x [N,H,W,cs_p], dy [N,OH,OW,cd_p] (and the bias gradient [cd_p] f32 from the same launch).
-    ``bias_dot`` (f32 [>= cout]) / ``dot`` (f32 [1]): dot += <bias_dot, unscaled bias gradient> (xmc_unpack_wgrad_bias_dot)."""
+    ``bias_dot`` (f32 [>= cout]) / ``dot`` (f32 [1]): dot += <bias_dot, unscaled bias gradient> (xmc_unpack_wgrad)."""
     staged = dy if isinstance(dy, _StagedMask) else None        # dy x LeakyReLU'(bits), masked where the kernel stages it
     if staged is not None:
         dy = staged.dy
@@ -692,7 +692,7 @@ def _conv_wgrad_raw(x, dy, geom, scale=None, up=False, want_bias=False, bias_dot
             d.dst = staged.materialised().data_ptr()
         with prof.launch("wgrad_kernel (conv weight gradient, MFMA + split-K atomics)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
                          f"wgrad {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, dy, dwp)):
-            L.check(L.load().xmc_conv_wgrad_bias(C.byref(d), _p(dwp), _p(gb), _st()), "xmc_conv_wgrad")
+            L.check(L.load().xmc_conv_wgrad(C.byref(d), _p(dwp), _p(gb), _st()), "xmc_conv_wgrad")
     return _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale, bias_dot, dot)
 
 
@@ -700,17 +700,10 @@ def _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale=None, bias_dot=None, dot=N
     """the packed accumulators of a weight-gradient launch (dwp f32 [k*k, rows, CS]; gb: the bias replicas or None) -> gw [Co,Ci,k,k],
     or (gw, bias gradient [CDy]) when gb is given"""
     gw = torch.empty((geom.cout, geom.cin // geom.groups, geom.k, geom.k), dtype=torch.float32, device=dwp.device)
-    if gb is not None:
-        assert geom.groups == 1
-        gbs = torch.empty(CDy, dtype=torch.float32, device=dwp.device)
-        assert (bias_dot is None) == (dot is None)
-        L.call("xmc_unpack_wgrad_bias_dot", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
-               _p(geom.perm_dev(dwp.device)), 0, _p(gb), _p(gbs), CDy, _p(bias_dot), _p(dot), _st())
-        return gw, gbs
-    assert bias_dot is None
-    L.call("xmc_unpack_wgrad_grouped", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
-           _p(geom.perm_dev(dwp.device)), 0, geom.groups, _st())
-    return gw
+    gbs = torch.empty(CDy, dtype=torch.float32, device=dwp.device) if gb is not None else None
+    L.call("xmc_unpack_wgrad", _p(dwp), _p(gw), geom.cout, geom.cin, geom.k, geom.k, rows, CS, _p(scale),
+           _p(geom.perm_dev(dwp.device)), 0, geom.groups, _p(gb), _p(gbs), CDy if gb is not None else 0, _p(bias_dot), _p(dot), _st())
+    return gw if gb is None else (gw, gbs)
 
 
 def _gtail_bwd_raw(dy, img, y, w, geom, want_w, want_bias, grid_cap=0):
@@ -771,7 +764,7 @@ def _affine_fwd_raw(x, ps, slope):
 def _affine_bwd_raw(x, dy, ps, slope, dx_acc=None, alpha=None, dot=None, want_sumpool=False):
     """-> dx, red [len(ps), N, C] (the gradients of ps).  ``dx_acc``: another gradient of x, added on the way out.
     ``alpha`` / ``dot`` (f32 [1] each): dy is the UNSCALED gradient from a consumer `sum + alpha * f(y)`: dot += <dy, y>, dy *= alpha
-    (xmc_affine2_act_bwd_dot).  ``want_sumpool``: -> dx, red, 2x2 sum pool of dx (same pass)."""
+    (xmc_affine2_act_bwd).  ``want_sumpool``: -> dx, red, 2x2 sum pool of dx (same pass)."""
     N, H, W, Cc = x.shape
     dx = torch.empty_like(x)
     if dx_acc is not None:
@@ -783,7 +776,7 @@ def _affine_bwd_raw(x, dy, ps, slope, dx_acc=None, alpha=None, dot=None, want_su
     rptrs = [_p(red[i]) for i in range(nred)] + ([] if nred == 4 else [None, None])
     assert (alpha is None) == (dot is None)
     dxp = torch.empty((N, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device) if want_sumpool else None
-    L.call("xmc_affine2_act_bwd_dot_pool", _p(x), _p(dy), *ptrs, _p(dx), *rptrs, _p(dx_acc), _p(alpha), _p(dot), _p(dxp), N, H, W, Cc,
+    L.call("xmc_affine2_act_bwd", _p(x), _p(dy), *ptrs, _p(dx), *rptrs, _p(dx_acc), _p(alpha), _p(dot), _p(dxp), N, H, W, Cc,
            float(slope), _code(x.dtype), _st())
     return (dx, red, dxp) if want_sumpool else (dx, red)
 

@@ -201,7 +201,7 @@ class DStemBlockFn(torch.autograd.Function):
     def _backward_bits(ctx, dout):
         nin = 13
         xin, h1, bits, w_img, b_img, w0, w2, ws, bs, gamma, wsets, D = ctx.saved_tensors
-        g_img, g0, g2, gs = ctx.geoms
+        g2 = ctx.geoms[2]
         dt = xin.dtype
         N, H, W, _ = xin.shape
         OH, OW = H // 2, W // 2
@@ -221,13 +221,8 @@ class DStemBlockFn(torch.autograd.Function):
         dx = None
         if need_x:
             # the gradient of the IMAGE (the G step's pass over the generated batch): the adjoint of the composed stem, one launch
-            # on the low-resolution gradients (+ the border corrections); "dstem_old_dgrad": the un-composed transposed chain
-            if "dstem_old_dgrad" in _DEBUG_DISPATCH:
-                dxp = _conv_dgrad_raw(dout, ws, gs, (OH, OW), dt)
-                dci = _conv_dgrad_raw(gh, w0, g0, (H, W), dt, res=dxp, res_rows=True, res_scale=0.25)
-                dx = _conv_dgrad_raw(dci, w_img, g_img, (H, W), dt)
-            else:
-                dx = _dstem_dgrad_raw(gh, dout, wsets, D, H, W)
+            # on the low-resolution gradients (+ the border corrections)
+            dx = _dstem_dgrad_raw(gh, dout, wsets, D, H, W)
         if skip_w or not any(ctx.needs_input_grad[1:7]):
             return (dx, None, None, None, dw2, None, None, dgamma) + (None,) * 5
         # gradients of the composed weights (every pixel) and of the border corrections (border pixels of h1), then back through the
@@ -674,7 +669,7 @@ def _attn_bwd_raw(key, q, x, stats, out, dctx, ncon, scale, dx_acc=None):
     dkey = torch.empty_like(key)
     dx = torch.empty_like(x) if dx_acc is None else dx_acc
     assert dx.shape == x.shape and dx.dtype == x.dtype and dx.is_contiguous()
-    L.call("xmc_attn_pool_bwd_acc", _p(key), _p(q), _p(x), _p(stats), _p(out), _p(dctx), _p(dq), _p(dkey), _p(dx), _p(dx_acc),
+    L.call("xmc_attn_pool_bwd", _p(key), _p(q), _p(x), _p(stats), _p(out), _p(dctx), _p(dq), _p(dkey), _p(dx), _p(dx_acc),
            N, H * W, ncon, pk, px, float(scale), _code(x.dtype), _st())
     return dkey, dq, dx
 

@@ -123,34 +123,50 @@ class HipAdam(torch.optim.Optimizer):
         for the tensors that have a gradient, in a launch of their own for the shadow tensors that have none -- and its update
         counter advances by one; a step the scaler skips leaves the shadow and the counter alone as well."""
         assert closure is None
-        if ema is not None:
-            return self._step_ema(grad_scale, scaler, ema)
-        groups = []
+        groups, fused = [], set()
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
             if not ps[0].is_cuda:
                 raise RuntimeError("HipAdam runs on the GPU only (no CPU fallback)")
-            groups.append((group, self._table(ps, ps[0].device)))
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if groups else None
-        if scaler is None:
-            for group, (tab, ch, nt, nc) in groups:
-                b1, b2 = group["betas"]
-                L.call("xmc_adam_step", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
-                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(grad_scale), st)
-        else:
+            groups.append((group, self._table(ps, ps[0].device), ema._table(ps, fused=True)[0] if ema is not None else None))
+            fused.update(id(p) for p in ps)
+        rest = [p for p in ema.params if id(p) not in fused] if ema is not None else []      # shadow tensors without a gradient
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if groups or rest else None
+        if scaler is not None:
             assert grad_scale == 1.0
-            CHECK, UPDATE, RESCALE = 1, 2, 4
-            # every group is checked before any is updated; the last update also ends the scaler's step
-            passes = [CHECK | UPDATE] if len(groups) == 1 else [CHECK, UPDATE]
-            for mode in passes:
-                for gi, (group, (tab, ch, nt, nc)) in enumerate(groups):
-                    b1, b2 = group["betas"]
-                    m = mode | (RESCALE if (mode & UPDATE) and gi == len(groups) - 1 else 0)
-                    L.call("xmc_adam_step_scaled", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
-                           float(group["lr"]), float(b1), float(b2), float(group["eps"]), C.c_void_p(scaler.sf.data_ptr()),
-                           C.c_void_p(scaler.si.data_ptr()), m, scaler.growth, scaler.backoff, scaler.interval, st)
+
+        def launch(group, table, etab, mode, bump):
+            """one `xmc_optim_step`: ``etab`` None = no shadow update in this launch"""
+            tab, ch, nt, nc = table
+            b1, b2 = group["betas"]
+            s = L.OptimStep(table=tab.data_ptr(), chunks=ch.data_ptr(), ntensors=nt, nchunks=nc, lr=float(group["lr"]), beta1=float(b1),
+                            beta2=float(b2), eps=float(group["eps"]), grad_scale=float(grad_scale), mode=mode)
+            if scaler is not None:
+                s.scale_dev, s.flags_dev = scaler.sf.data_ptr(), scaler.si.data_ptr()
+                s.growth, s.backoff, s.interval = scaler.growth, scaler.backoff, scaler.interval
+            if etab is not None:
+                s.ema_table, s.num_updates_dev, s.bump = etab.data_ptr(), ema.num_updates.data_ptr(), bump
+                s.decay, s.start = ema.decay, ema.start
+            L.call("xmc_optim_step", C.byref(s), st)
+
+        one_call = len(groups) == 1 and not rest       # check, update and rescale in one call
+        if scaler is not None and not one_call:
+            # every group is checked before any tensor (or shadow) is updated; the last update also ends the scaler's step
+            for group, table, _ in groups:
+                launch(group, table, None, L.ADAM_CHECK, 0)
+        if rest:        # (reads the found-inf flag, so before the launch that clears it; bumps the counter only if it is the last launch)
+            etab, ech, ent, enc = ema._table(rest)
+            L.call("xmc_ema_step", C.c_void_p(etab.data_ptr()), ent, C.c_void_p(ech.data_ptr()), enc, float(ema.decay), int(ema.start),
+                   C.c_void_p(ema.num_updates.data_ptr()), C.c_void_p(scaler.si.data_ptr()) if scaler is not None else None,
+                   0 if groups else 1, st)
+        for gi, (group, table, etab) in enumerate(groups):
+            last = gi == len(groups) - 1
+            mode = L.ADAM_UPDATE
+            if scaler is not None:
+                mode |= (L.ADAM_CHECK if one_call else 0) | (L.ADAM_RESCALE if last else 0)
+            launch(group, table, etab, mode, 1 if last else 0)
         self._repack()
 
     def _repack(self):
@@ -160,52 +176,6 @@ class HipAdam(torch.optim.Optimizer):
         for p in changed:
             p._xmc_epoch = getattr(p, "_xmc_epoch", 0) + 1
         ops.repack_params(changed)
-
-    def _step_ema(self, grad_scale, scaler, ema):
-        """`step` with the shadow update of ``ema``: the same launches with `xmc_adam_ema_step[_scaled]` in the place of
-        `xmc_adam_step[_scaled]`, plus one `xmc_ema_step` for the shadow tensors whose parameter has no gradient."""
-        groups, fused = [], set()
-        for group in self.param_groups:
-            ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
-                continue
-            if not ps[0].is_cuda:
-                raise RuntimeError("HipAdam runs on the GPU only (no CPU fallback)")
-            groups.append((group, self._table(ps, ps[0].device), ema._table(ps, fused=True)))
-            fused.update(id(p) for p in ps)
-        rest = [p for p in ema.params if id(p) not in fused]
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        nupd = C.c_void_p(ema.num_updates.data_ptr())
-        decay, start = float(ema.decay), int(ema.start)
-        flag = C.c_void_p(scaler.si.data_ptr()) if scaler is not None else None
-        CHECK, UPDATE, RESCALE = 1, 2, 4
-        one_call = len(groups) == 1 and not rest       # check, update and rescale in one call, as without a shadow set
-        if scaler is not None:
-            assert grad_scale == 1.0
-        if scaler is not None and not one_call:
-            # every group is checked before any tensor (or shadow) is updated; the last update also ends the scaler's step
-            for group, (tab, ch, nt, nc), _ in groups:
-                b1, b2 = group["betas"]
-                L.call("xmc_adam_step_scaled", C.c_void_p(tab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
-                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), C.c_void_p(scaler.sf.data_ptr()),
-                       flag, CHECK, scaler.growth, scaler.backoff, scaler.interval, st)
-        if rest:        # (reads the found-inf flag, so before the launch that clears it; bumps the counter only if it is the last launch)
-            etab, ech, ent, enc = ema._table(rest)
-            L.call("xmc_ema_step", C.c_void_p(etab.data_ptr()), ent, C.c_void_p(ech.data_ptr()), enc, decay, start, nupd, flag,
-                   0 if groups else 1, st)
-        for gi, (group, (tab, ch, nt, nc), (etab, _, _, _)) in enumerate(groups):
-            b1, b2 = group["betas"]
-            last = gi == len(groups) - 1
-            if scaler is None:
-                L.call("xmc_adam_ema_step", C.c_void_p(tab.data_ptr()), C.c_void_p(etab.data_ptr()), nt, C.c_void_p(ch.data_ptr()), nc,
-                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(grad_scale), decay, start, nupd,
-                       1 if last else 0, st)
-            else:
-                L.call("xmc_adam_ema_step_scaled", C.c_void_p(tab.data_ptr()), C.c_void_p(etab.data_ptr()), nt,
-                       C.c_void_p(ch.data_ptr()), nc, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                       C.c_void_p(scaler.sf.data_ptr()), flag, (CHECK if one_call else 0) | UPDATE | (RESCALE if last else 0), scaler.growth, scaler.backoff,
-                       scaler.interval, decay, start, nupd, 1 if last else 0, st)
-        self._repack()
 
 
 class ParamEMA:
