@@ -63,7 +63,9 @@ extern "C" {
  *     Merged, the widest argument list under the shortest name, every optional pointer nullable:
  *     xmc_affine2_act_bwd <- _acc / _dot / _dot_pool (now takes N, H, W);  xmc_attn_pool_bwd <- _acc (dx_acc);
  *     xmc_conv_wgrad <- _bias (dbias);  xmc_unpack_wgrad <- _grouped / _bias / _bias_dot (groups, gb_replicas, gb, CD, bias_dot, dot).
- *     XmcOptimStep + xmc_optim_step replace xmc_adam_step, xmc_adam_step_scaled, xmc_adam_ema_step and xmc_adam_ema_step_scaled. */
+ *     XmcOptimStep + xmc_optim_step replace xmc_adam_step, xmc_adam_step_scaled, xmc_adam_ema_step and xmc_adam_ema_step_scaled.
+ *     Added under 13 (additions only): xmc_clip_resize_h_u8 / xmc_clip_resize_v_u8 / xmc_attention_causal / xmc_bias_quick_gelu /
+ *     xmc_clip_vision_embed / xmc_clip_text_embed / xmc_clip_pool_ln / xmc_clip_cosine (csrc/clip.hip). */
 #define XMC_ABI_VERSION 13
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -380,6 +382,40 @@ int xmc_attention_short(const float* qkv, const int32_t* lens, void* out, int B,
 int xmc_bias_gelu(const float* x, const float* bias, void* out, int64_t rows, int F, int out_dtype, void* stream);
 int xmc_sbert_pool(const float* hidden, const int32_t* lens, float* words, float* sent, uint8_t* mask, int B, int T, int H, int L,
                    int normalize, void* stream);
+/* CLIPScore (csrc/clip.hip): what the CLIP ViT-B/32 towers need besides the f32 GEMMs and the kernels above.  Forward only, f32 in both
+ * builds, no atomics: the same inputs give the same bytes.  H (a tower's width): a multiple of 64, <= 1024.
+ *
+ * clip_resize_h_u8 / clip_resize_v_u8: PIL.Image.resize(BICUBIC) (Pillow's Resample.c) on uint8 RGB, bit for bit, one axis per call.
+ *   `bounds` int32 [out][2] = (first source sample, number of samples), `coeffs` int32 [out][ksize] = the normalised filter weights
+ *   with 22 fraction bits, both computed by the caller in f64; every output is clip8((2^21 + sum sample * k) >> 22) in int32 (the caller
+ *   checks 255 * sum |k| + 2^21 < 2^31).  The kernels clamp a window to the source, so a bad table reads nothing outside it.
+ *   h: src [N,H,W,3] -> dst [N,H,OW,3].
+ *   v: src [N,H,W,3] -> mode 0: dst uint8 [N,OH,W,3];  mode 1: the S x S crop at (top, left) of the [OH,W] result, each channel through
+ *   `lut` f32 [3][256], written patch-major as f32 [N*(S/P)^2, 3*P*P]: row (n, y/P, x/P), column c*P*P + (y%P)*P + x%P (the flatten order
+ *   of a ViT patch_embedding.weight, so the patch embedding is a plain GEMM).  S % P == 0, top + S <= OH, left + S <= W.
+ * attention_causal: attention_short's layout (qkv f32 [B*T,3H], head_dim 64, 1 <= T <= 64) over keys j <= i, every row valid;
+ *   out f32 [B*T,H].  Query 0 returns v[0]; every row is finite.
+ * bias_quick_gelu: out [rows,F] = v * sigmoid(1.702 v), v = x + bias; F % 8 == 0; finite for every finite v.
+ * clip_vision_embed: out [N*(GG+1),H] = LN(row) * gamma + beta, row 0 of an image = cls + pos[0], row 1+p = patch[n*GG+p] + pos[1+p];
+ *   patch [N*GG,H], pos [GG+1,H].  One wave per row, two-pass f32 statistics.
+ * clip_text_embed: out [B*T,H] = tok[ids[b,t]] + pos[t]; ids int64 [B,T], tok [vocab,H], pos [npos,H], T <= npos.  An id outside
+ *   [0, vocab) gives a zero row (the host wrapper validates ids it can see).
+ * clip_pool_ln: out [B,H] = LN(x[b, index[b]]) * gamma + beta; x [B*T,H], index int32 [B] clamped to [0, T).
+ * clip_cosine: out [N] = <img[n], txt[m]> / (|img[n]| |txt[m]|), m = caption_of_image[n] (int32 [N], clamped to [0, M)) or n when it is
+ *   NULL (then N <= M); img [N,D], txt [M,D].  One wave per image, fixed summation order. */
+int xmc_clip_resize_h_u8(const uint8_t* src, uint8_t* dst, const int32_t* bounds, const int32_t* coeffs, int N, int H, int W, int OW,
+                         int ksize, void* stream);
+int xmc_clip_resize_v_u8(const uint8_t* src, void* dst, const int32_t* bounds, const int32_t* coeffs, const float* lut, int N, int H, int W,
+                         int OH, int ksize, int mode, int S, int P, int top, int left, void* stream);
+int xmc_attention_causal(const float* qkv, float* out, int B, int T, int heads, int head_dim, void* stream);
+int xmc_bias_quick_gelu(const float* x, const float* bias, float* out, int64_t rows, int F, void* stream);
+int xmc_clip_vision_embed(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta, float* out, int N,
+                          int GG, int H, float eps, void* stream);
+int xmc_clip_text_embed(const int64_t* ids, const float* tok, const float* pos, float* out, int B, int T, int H, int64_t vocab, int npos,
+                        void* stream);
+int xmc_clip_pool_ln(const float* x, const int32_t* index, const float* gamma, const float* beta, float* out, int B, int T, int H, float eps,
+                     void* stream);
+int xmc_clip_cosine(const float* img, const float* txt, const int32_t* caption_of_image, float* out, int N, int M, int D, void* stream);
 /* Spectral normalisation of a layer weight: the legacy torch.nn.utils.spectral_norm hook the reference's layer factories apply
  * when DISC.SPEC_NORM is set (model/modules.py:3,16-17,31-32).  W: f32 [R,C] row-major (the parameter weight_orig viewed as
  * [out, in*k*k]); u [R], v [C]: the hook's weight_u / weight_v buffers.  training != 0: one power iteration, IN PLACE

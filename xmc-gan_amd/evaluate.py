@@ -1,12 +1,13 @@
 """The evaluation pipeline behind ``train_gan.eval()``, ``sample.py`` and the scoring command lines ("The evaluation pipeline"):
 where a metric's weights come from, the loaded models, and ``MetricSuite`` -- FID, precision / recall / density / coverage (PRDC),
-R-precision, KID and the Inception Score over one pass of the images.  Nothing but ``os`` is imported until a metric is asked for."""
+R-precision, KID, the Inception Score and CLIPScore over one pass of the images.  Nothing but ``os`` is imported until a metric is asked for."""
 import os
 
 FID, PRDC, RPREC, KID, IS = "FID", "PRDC", "R-precision", "KID", "IS"
+CLIP = "CLIPScore"
 CACHE_FILES = {FID: "org_stats.npz", PRDC: "org_features.npz", KID: "org_features.npz"}       # eval()'s real side, beside org_dir (PRDC and KID: one file)
 _WHAT = {"XMC_FID_INCEPTION": "FID Inception weights", "XMC_DAMSM_IMAGE_ENCODER": "DAMSM image encoder weights"}
-_models = {}            # 'inception' / 'damsm' -> (key, model): one loaded model per kind (`load_model`)
+_models = {}            # 'inception' / 'damsm' / 'clip' -> (key, model): one loaded model per kind (`load_model`)
 
 
 def resolve_weights(given, env_name, flag, must_exist=True, refusal=None):
@@ -31,15 +32,19 @@ def image_set_kind(path):
 
 
 def load_model(kind, path, device):
-    """the Inception extractor ('inception') or DAMSM image encoder ('damsm') of a weights file: one per kind, reloaded when the file, its
-    modification time or the device is another"""
+    """the Inception extractor ('inception') or DAMSM image encoder ('damsm') of a weights file, or the CLIP scorer ('clip') of a model
+    directory: one per kind, reloaded when the file (the directory's config.json), its modification time or the device is another"""
     import torch
-    key = (os.path.abspath(path), os.stat(path).st_mtime_ns if os.path.isfile(path) else None, str(torch.device(device)))
+    stamp = os.path.join(path, "config.json") if kind == "clip" else path
+    key = (os.path.abspath(path), os.stat(stamp).st_mtime_ns if os.path.isfile(stamp) else None, str(torch.device(device)))
     if _models.get(kind, (None, None))[0] != key:
         _models.pop(kind, None)
         if kind == "inception":
             from . import fid as F
             _models[kind] = key, F.InceptionFID(path, device)
+        elif kind == "clip":
+            from . import clip as CL
+            _models[kind] = key, CL.CLIPScorer(path, device)
         else:
             from . import rprecision as RP
             _models[kind] = key, RP.load_image_encoder(path, None, device)
@@ -55,10 +60,11 @@ class MetricSuite:
     where a file for another count kept them from being gathered, those of one more pass over the real images -- and is written.
     ``kid``: the Kernel Inception Distance over ``kid_subsets`` subsets of ``kid_subset_size`` rows; it is two-sided, takes the feature rows
     and shares PRDC's bank and cache file: with both on, the rows are stored, read and written once.  ``inception_score`` > 0: the Inception
-    Score over that many splits, one-sided like R-precision."""
+    Score over that many splits, one-sided like R-precision.  ``clip_dir``: CLIPScore with the CLIP model directory there, one-sided, from the
+    caption strings ``update_fake`` is given."""
 
     def __init__(self, device, fid_inception="", prdc_k=0, damsm_image_encoder="", text_encoder=None, rp_k=100, rp_splits=10, rp_seed=0, fid=True,
-                 kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0, inception_score=0):
+                 kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0, inception_score=0, clip_dir=""):
         self.device, self.prdc_k, self.why = device, int(prdc_k), {}
         self.kid_args, is_splits = (int(kid_subsets), int(kid_subset_size), int(kid_seed)), int(inception_score)
         self.extractor = self.encoder = self._cache_dir = None
@@ -93,6 +99,9 @@ class MetricSuite:
                 self.fake[RPREC] = RP.RPrecision(rp_k, rp_splits, rp_seed)
             else:
                 self.why[RPREC] = why
+        if clip_dir:
+            from .clip import CLIPScoreStats
+            self.fake[CLIP] = CLIPScoreStats(load_model("clip", clip_dir, device))
         self._rows = PRDC if PRDC in self.fake else KID                # the metric the bank of rows and its real side are kept under
         self._two_sided = [m for m in (FID, self._rows) if m in self.fake]
 
@@ -109,8 +118,9 @@ class MetricSuite:
                 self._gathered[m] = type(self.fake[m])(device=self.device)
             self._gathered[m].update(feats)
 
-    def update_fake(self, images, sent_embs=None, caption_of_image=None):
-        """generated images ([B,3,H,W] floats or uint8 [B,H,W,3]); for R-precision their sentence codes and, where images share one, each image's row"""
+    def update_fake(self, images, sent_embs=None, caption_of_image=None, captions=None):
+        """generated images ([B,3,H,W] floats or uint8 [B,H,W,3]); for R-precision their sentence codes and, where images share one, each image's
+        row; for CLIPScore their caption strings (one per image, or fewer and each image's row): a batch without them is not scored"""
         if not self.fake:
             return
         u8 = self._u8(images)
@@ -120,6 +130,8 @@ class MetricSuite:
                 self.fake[m].update(feats)
         if RPREC in self.fake:
             self.fake[RPREC].update(self.encoder.encode_u8(u8)[1], sent_embs, caption_of_image)
+        if CLIP in self.fake and captions is not None:
+            self.fake[CLIP].update(u8, captions, caption_of_image)
 
     @property
     def wants_real(self):
@@ -192,8 +204,9 @@ class MetricSuite:
         return MF.kid(self.real[KID if KID in self.real else self._rows](), self.fake[KID], subsets, size, seed)
 
     def results(self):
-        """yields (metric, values or None, why not or None) for every metric asked for, in the order FID, PRDC, R-precision, KID, IS; values:
-        dict(FID=x), `manifold.prdc`'s dict, `RPrecision.finalize`'s dict, `manifold.kid`'s dict, `InceptionScore.finalize`'s dict.  A
+        """yields (metric, values or None, why not or None) for every metric asked for, in the order FID, PRDC, R-precision, KID, IS, CLIPScore; values:
+        dict(FID=x), `manifold.prdc`'s dict, `RPrecision.finalize`'s dict, `manifold.kid`'s dict, `InceptionScore.finalize`'s dict,
+        `CLIPScoreStats.finalize`'s dict.  A
         ValueError of theirs is the reason."""
         if FID in self.fake and self.fake[FID].n < 2:
             yield FID, None, "fewer than two images"
@@ -201,7 +214,7 @@ class MetricSuite:
             from .fid import frechet_distance
             yield FID, dict(FID=frechet_distance(*self.real[FID](), *self.fake[FID].finalize())), None
         for metric, compute in ((PRDC, self._prdc), (RPREC, lambda: self.fake[RPREC].finalize()), (KID, self._kid),
-                                (IS, lambda: self.fake[IS].finalize())):
+                                (IS, lambda: self.fake[IS].finalize()), (CLIP, lambda: self.fake[CLIP].finalize())):
             values, why = None, self.why.get(metric)
             if metric in self.fake:
                 try:

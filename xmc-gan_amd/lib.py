@@ -187,6 +187,14 @@ _SIGS = {
     "xmc_poly_mmd_sums": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
     "xmc_inception_score_ws_bytes": [i32, i32, i32],
     "xmc_inception_score": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
+    "xmc_clip_resize_h_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "xmc_clip_resize_v_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "xmc_attention_causal": [vp, vp, i32, i32, i32, i32, vp],
+    "xmc_bias_quick_gelu": [vp, vp, vp, i64, i32, vp],
+    "xmc_clip_vision_embed": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+    "xmc_clip_text_embed": [vp, vp, vp, vp, i32, i32, i32, i64, i32, vp],
+    "xmc_clip_pool_ln": [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+    "xmc_clip_cosine": [vp, vp, vp, vp, i32, i32, i32, vp],
 }
 _RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p,
             "xmc_inception_score_ws_bytes": i64}

@@ -4,7 +4,7 @@
                              (--captions FILE | --token_ids FILE.npy | --synthetic N) [--n_per_caption K --seed S --truncation PSI]
                              [--best_of M --netD netD_*.pth] [--walk N] [--interp_sent N] [--grid_max N] [--no_png]
                              [--fid_against DIR_OR_NPZ --fid_inception PATH] [--prdc_against DIR_OR_FEATURES_NPZ [--prdc_k K]]
-                             [--rprecision --damsm_image_encoder PATH]
+                             [--rprecision --damsm_image_encoder PATH] [--clip_score --clip_dir PATH]
                              [--kid_against DIR_OR_FEATURES_NPZ [--kid_subsets S --kid_subset_size M]] [--inception_score [--is_splits S]]
 
 Writes ``<out>/<caption index:05d>_<k>.png`` (K images per caption), ``<out>/grid.png`` (the first ``--grid_max`` of them, every image min-max scaled
@@ -81,6 +81,10 @@ def parse_args(argv=None):
                         help='score the sampled images: R-precision against their captions (RNN presets) -> manifest "r_precision"')
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
                         help="DAMSM image encoder weights for --rprecision (image_encoder100.pth; default: $XMC_DAMSM_IMAGE_ENCODER)")
+    parser.add_argument('--clip_score', action='store_true',
+                        help='score the sampled images: CLIPScore against the sentences of --captions -> manifest "clip_score"')
+    parser.add_argument('--clip_dir', type=str, default='', metavar='PATH',
+                        help='--clip_score: a Hugging Face CLIPModel directory, e.g. a copy of openai/clip-vit-base-patch32 (default: $XMC_CLIP_DIR)')
     parser.add_argument('--rp_k', type=int, default=100, metavar='K', help='--rprecision: candidates per image, the own caption included')
     parser.add_argument('--rp_splits', type=int, default=10, metavar='S', help='--rprecision: parts the mean and its spread are taken over')
     # reranking
@@ -135,6 +139,12 @@ def _check_args(args):
                                                    refusal='--rprecision needs the DAMSM image encoder weights')
         if args.rp_k < 2 or args.rp_splits < 1:
             raise SystemExit('--rp_k must be >= 2 and --rp_splits >= 1')
+    if args.clip_score:
+        args.clip_dir = args.clip_dir or os.environ.get('XMC_CLIP_DIR', '')
+        if not os.path.isfile(os.path.join(args.clip_dir, 'config.json')):
+            raise SystemExit(f'--clip_score needs a CLIP model directory: --clip_dir PATH or XMC_CLIP_DIR (got {args.clip_dir!r})')
+        if not args.captions:
+            raise SystemExit('--clip_score compares the images with the sentences of --captions FILE; --token_ids and --synthetic hold no text')
     cfg_from_file(args.cfg)
     if args.imsize != -1:
         cfg.IMG.SIZE = args.imsize
@@ -211,6 +221,7 @@ _SCORES = {     # metric of MetricSuite.results(): (the flag that asked for it, 
     'R-precision': ('--rprecision', 'R-precision: {r_precision} +- {std} (k={k}, n={n})', 'r_precision'),
     'KID': ('--kid_against', 'KID: {kid} +- {std} (subsets={subsets}, size={subset_size}, n={n_real}/{n_fake})', 'kid'),
     'IS': ('--inception_score', 'IS: {inception_score} +- {std} (splits={splits}, n={n})', 'inception_score'),
+    'CLIPScore': ('--clip_score', 'CLIPScore: {clip_score} +- {std} (n={n}, model={model})', 'clip_score'),
 }
 
 
@@ -273,7 +284,13 @@ def main(argv=None):
         more.update(kid=True, kid_subsets=args.kid_subsets, kid_subset_size=args.kid_subset_size, kid_seed=args.seed)
     if args.inception_score:
         more.update(inception_score=args.is_splits)
-    suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against or more) else '', args.prdc_k if args.prdc_against else 0,
+    if args.clip_score:
+        more.update(clip_dir=args.clip_dir)
+        try:
+            load_model('clip', args.clip_dir, device)
+        except (ImportError, ValueError, NotImplementedError) as e:
+            raise SystemExit(f'--clip_dir: {e}')
+    suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against or args.kid_against or args.inception_score) else '', args.prdc_k if args.prdc_against else 0,
                         args.damsm_image_encoder if args.rprecision else '', text_encoder, args.rp_k, args.rp_splits, args.seed,
                         fid=bool(args.fid_against), **more)
     for metric, why in suite.why.items():
@@ -294,7 +311,11 @@ def main(argv=None):
                 u8, sc = ops.image_to_u8(x8), None
             if c0 * K < n_grid:
                 kept[c0 * K:min(n_grid, c1 * K)] = x8[:n_grid - c0 * K]
-            suite.update_fake(u8, sents[c0:c1], torch.arange(nc).repeat_interleave(K))       # image r of the batch was made from caption r // K
+            pairing = torch.arange(nc).repeat_interleave(K)          # image r of the batch was made from caption r // K
+            if args.clip_score:
+                suite.update_fake(u8, sents[c0:c1], pairing, captions=lines[c0:c1])
+            else:
+                suite.update_fake(u8, sents[c0:c1], pairing)
             host = u8.cpu().numpy()                                  # one copy per batch: 3 bytes per pixel
             for r in range(nc * K):
                 c, k = c0 + r // K, r % K
@@ -339,7 +360,7 @@ def main(argv=None):
                     cfg=os.path.abspath(args.cfg), config_name=cfg.CONFIG_NAME, generator=cfg.GEN.ENCODER_NAME, img_size=S,
                     seed=args.seed, precision=ops.precision(), truncation=args.truncation, n_per_caption=K, best_of=args.best_of or None,
                     captions=n, fid=scores.pop('fid', {}).get('FID'), grid=grid, grid_images=n_grid, walks=walks, interps=interps, images=images)
-    manifest.update({key: scores[key] for key in ('r_precision', 'prdc', 'kid', 'inception_score') if key in scores})     # (only when asked for, in the order of before)
+    manifest.update({key: scores[key] for key in ('r_precision', 'prdc', 'kid', 'inception_score', 'clip_score') if key in scores})     # (only when asked for, in the order of before)
     with open(os.path.join(args.out, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     torch.cuda.synchronize()

@@ -100,6 +100,10 @@ def parse_args(argv=None):
     parser.add_argument('--damsm_image_encoder', type=str, default='', metavar='PATH',
                         help="DAMSM image encoder weights (image_encoder100.pth of AttnGAN's DAMSM archive): eval() also reports R-precision "
                              "(RNN presets; default: $XMC_DAMSM_IMAGE_ENCODER; without either, no R-precision)")
+    parser.add_argument('--clip_dir', type=str, default='', metavar='PATH',
+                        help='a Hugging Face CLIPModel directory (config.json, weights, tokenizer.json; e.g. a copy of '
+                             'openai/clip-vit-base-patch32): eval() also reports CLIPScore of the generated images against their captions '
+                             '(default: $XMC_CLIP_DIR; without either, no CLIPScore)')
     parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
                         help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (config.json, weights, tokenizer '
                              'files; default: $XMC_SBERT_DIR).  Without it the SBERT presets run with --synthetic only')
@@ -682,7 +686,7 @@ def load_average(model_dir, epoch, ema, device, logger):
 
 
 def _end_of_epoch(epoch, last, *, netG, netD, optimizerG, optimizerD, ema, netG_ema, fixed, img_dir, model_dir, test_loader, text_encoder,
-                  logger, writer, eval_opts):
+                  logger, writer, eval_opts, clip_dir=None):
     """what the reference does after an epoch's last batch (train_gan.py:300-336): scalars, the sample grid from the fixed batch, and past
     epoch 50 the checkpoint and `eval`; with ``ema`` the grid, the checkpoint and `eval` take the averaged generator"""
     if parallel.rank() == 0:
@@ -709,11 +713,11 @@ def _end_of_epoch(epoch, last, *, netG, netD, optimizerG, optimizerD, ema, netG_
             # (--caption_cache: the test split's rows are another table; the train split's encoder carries the test split's)
             eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder, netG=gen,
                  logger=logger, num_samples=6000, save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None,
-                 writer=writer, eval_opts=eval_opts)
+                 writer=writer, eval_opts=eval_opts, clip_dir=clip_dir)
 
 
 def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, optimizerG, optimizerD, logger, model_dir,
-          opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None):
+          opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None, clip_dir=None):
     """Epoch loop with the reference's signature (train_gan.py:142); returns the last iteration's losses.
 
     With ``img_dir`` (rank 0) it keeps the reference's visual log: ``sents.txt`` and ``imgs.png`` of the first batch (146-160),
@@ -730,7 +734,7 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
     add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training.
 
     ``opts.diffaug`` (a `DiffAugment`, ``--diffaug``): its rows are redrawn before every iteration, graphed or eager.
-    ``eval_opts`` (an `EvalOptions`): what `eval` scores after an epoch, handed on to it."""
+    ``eval_opts`` (an `EvalOptions`) and ``clip_dir`` (CLIPScore's model directory): what `eval` scores after an epoch, handed on to it."""
     device = next(netG.parameters()).device
     opts = opts or StepOptions()
     ema = opts.ema
@@ -783,7 +787,7 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
         clock.after_epoch(nsteps, runner.hipgraph)
         _end_of_epoch(epoch, last, netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, ema=ema, netG_ema=netG_ema,
                       fixed=fixed, img_dir=img_dir, model_dir=model_dir, test_loader=test_loader, text_encoder=text_encoder,
-                      logger=logger, writer=writer, eval_opts=eval_opts)
+                      logger=logger, writer=writer, eval_opts=eval_opts, clip_dir=clip_dir)
     return finish()
 
 
@@ -807,11 +811,26 @@ _EVAL_REPORT = {    # metric of MetricSuite.results(): (its log line, the values
             ' epoch {epoch}, KID not computed: {why}'),
     'IS': (' epoch {epoch}, IS : {inception_score} +- {std} (splits={splits}, n={n})', ('inception_score',),
            ' epoch {epoch}, IS not computed: {why}'),
+    'CLIPScore': (' epoch {epoch}, CLIPScore : {clip_score} +- {std} (n={n}, model={model})', ('clip_score',),
+                  ' epoch {epoch}, CLIPScore not computed: {why}'),
 }
-_EVAL_SCALAR = {'r_precision': 'R_precision', 'kid': 'KID', 'inception_score': 'IS'}     # a value's name -> its scalar's
+_EVAL_SCALAR = {'r_precision': 'R_precision', 'kid': 'KID', 'inception_score': 'IS', 'clip_score': 'CLIPScore'}     # a value's name -> its scalar's
 _EVAL_METRICS_KEY = {('PRDC', 'k'): 'prdc_k', ('KID', 'std'): 'kid_std', ('KID', 'subsets'): 'kid_subsets', ('KID', 'subset_size'): 'kid_subset_size',
                      ('KID', 'n_real'): 'kid_n_real', ('KID', 'n_fake'): 'kid_n_fake',
-                     ('IS', 'std'): 'inception_score_std', ('IS', 'splits'): 'inception_score_splits', ('IS', 'n'): 'inception_score_n'}
+                     ('IS', 'std'): 'inception_score_std', ('IS', 'splits'): 'inception_score_splits', ('IS', 'n'): 'inception_score_n',
+                     ('CLIPScore', 'std'): 'clip_score_std', ('CLIPScore', 'cosine'): 'clip_score_cosine', ('CLIPScore', 'n'): 'clip_score_n',
+                     ('CLIPScore', 'n_truncated'): 'clip_score_n_truncated', ('CLIPScore', 'model'): 'clip_score_model'}
+
+
+def _caption_strings(caps, cap_lens, loader):
+    """the caption strings of a batch for CLIPScore: SENT captions as they are, WORD captions through the dataset's ``i2w``; None where
+    neither is there (--synthetic)"""
+    if len(caps) and all(isinstance(c, str) for c in caps):
+        return list(caps)
+    i2w = getattr(getattr(loader, 'dataset', None), 'i2w', None)
+    if not i2w or not torch.is_tensor(caps):
+        return None
+    return [' '.join(i2w[t] for t in row[:n]) for row, n in zip(caps.tolist(), torch.as_tensor(cap_lens).tolist())]
 
 
 def _new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score):
@@ -830,14 +849,15 @@ def _new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score):
 @torch.no_grad()
 def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
          damsm_image_encoder=None, metrics=None, prdc=None, eval_opts=None, kid=None, kid_subsets=None, kid_subset_size=None,
-         inception_score=None):
+         inception_score=None, clip_dir=None):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to ``save_dir/<key>.png`` and,
     unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``, as 8-bit PNGs of (x + 1) * 127.5.  The
     scores are a `MetricSuite`'s (xmc_gan_amd/evaluate.py): FID with ``fid_inception`` (without it: between the two directories, when
     ``pytorch_fid`` imports), precision / recall / density / coverage with ``prdc`` = K > 0 beside it, R-precision with ``damsm_image_encoder``
     and an ``RNN_ENCODER``, the Kernel Inception Distance with ``kid`` (over ``kid_subsets`` subsets of ``kid_subset_size`` rows) and the
     Inception Score with ``inception_score`` = SPLITS > 0, both from the same Inception features; each is the keyword, else ``eval_opts``,
-    else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER.  With ``org_dir`` the real side is cached beside it.  Every score is logged (or one
+    else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER; CLIPScore with ``clip_dir`` (a CLIP model directory), from the caption strings of the
+    batches (SENT captions, or WORD captions through the dataset's ``i2w``; 'clip_score_*' in ``metrics``).  With ``org_dir`` the real side is cached beside it.  Every score is logged (or one
     line says why there is none), written to ``writer`` and, FID apart, put into ``metrics`` when a dict is passed ('k' of PRDC as 'prdc_k';
     of KID and IS every name but 'kid' / 'inception_score' carries that word as a prefix: 'kid_std', 'kid_n_real', 'inception_score_n', ...).  Returns (uint8 tensor of the generated images,
     FID or None)."""
@@ -854,7 +874,7 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     suite = MetricSuite(device, fid_inception or given.fid_inception or os.environ.get('XMC_FID_INCEPTION', ''),
                         given.prdc_k if prdc is None else prdc,
                         damsm_image_encoder or given.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', ''), text_encoder,
-                        **_new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score))
+                        **_new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score), **({'clip_dir': clip_dir} if clip_dir else {}))
     if org_dir:
         suite.open_cache(os.path.dirname(os.path.abspath(org_dir)))
     cnt, outs = 0, []
@@ -864,7 +884,10 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
         noise = torch.randn(sent_embs.size(0), cfg.TRAIN.NOISE_DIM).to(device)
         fake = netG(noise=noise, sent_embs=sent_embs, words_embs=words_embs, mask=mask)
         outs.append(((fake + 1.0) * 127.5).clamp(0, 255).to(torch.uint8).cpu())
-        suite.update_fake(fake, sent_embs)
+        if clip_dir:
+            suite.update_fake(fake, sent_embs, captions=_caption_strings(caps, cap_lens, loader))
+        else:
+            suite.update_fake(fake, sent_embs)
         suite.update_real(imgs)              # (taken only while a metric lacks its real side)
         for j in range(fake.size(0)):
             if save_dir:
@@ -1012,6 +1035,9 @@ def _checked_args(argv):
     eval_opts = EvalOptions(fid_inception, args.prdc,
                             resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False),
                             args.kid, args.kid_subsets, args.kid_subset_size, args.inception_score)
+    args.clip_dir = args.clip_dir or os.environ.get('XMC_CLIP_DIR', '')
+    if args.clip_dir and not os.path.isfile(os.path.join(args.clip_dir, 'config.json')):
+        raise SystemExit(f'--clip_dir: {args.clip_dir} is not a CLIP model directory (no config.json)')
     return args, aug_policy, eval_opts
 
 
@@ -1097,7 +1123,7 @@ def main(argv=None):
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
                  opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
                                   ema=ema, diffaug=aug),
-                 img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts)
+                 img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts, clip_dir=args.clip_dir or None)
     if writer is not None:
         writer.close()
     torch.cuda.synchronize()
