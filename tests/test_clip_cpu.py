@@ -225,7 +225,7 @@ def test_header_binding_makefile_and_ops_agree_on_the_entry_points():
     assert "atomic" not in src.split("#include")[1]                      # one writer per element, a fixed order
     for name in ("resize_bicubic_u8", "clip_patch_rows", "attention_causal", "bias_quick_gelu", "clip_vision_embed", "clip_text_embed",
                  "clip_pool_ln", "clip_cosine"):
-        assert callable(getattr(ops, name)) and getattr(ops, name).__module__.endswith("ops._nodes_conv")
+        assert callable(getattr(ops, name)) and getattr(ops, name).__module__.endswith("ops._forward")
     for variant in ("bf16", "f16"):
         lib = L.load(variant)
         assert lib.xmc_abi_version() == 13 and all(hasattr(lib, n) for n in ENTRY_POINTS)

@@ -184,6 +184,36 @@ def test_cosine_rows_and_pairing():
         ops.clip_cosine(img.to(DEV), txt.to(DEV))                     # seven images, three captions, no pairing
 
 
+# ------------------------------------------------------------------------------------------ one copy of the device code, bit for bit
+@pytest.mark.parametrize("T", [7, 64])
+def test_causal_attention_is_short_attention_with_growing_lengths(T):
+    """one sample T times with the lengths 1 .. T: query b of the sample that is b + 1 tokens long sees the keys 0 .. b, as causal query b does"""
+    heads = 2
+    H = heads * 64
+    qkv = _rn(T, 3 * H, seed=40 + T).to(DEV)
+    lens = torch.arange(1, T + 1, dtype=torch.int32, device=DEV)
+    short = ops.attention_short(qkv.repeat(T, 1), lens, T, T, heads).view(T, T, H)
+    causal = ops.attention_causal(qkv, 1, T, heads)
+    assert torch.equal(short[torch.arange(T), torch.arange(T)], causal)
+
+
+@pytest.mark.parametrize("width", [128, 768])
+def test_embed_and_pool_layernorms_are_add_layernorm(width):
+    """the LayerNorm of `clip_pool_ln` and of `clip_vision_embed` on rows that `add_layernorm` is handed ready-made"""
+    N, GG, T = 3, 4, 5
+    d = lambda t: t.to(DEV).contiguous()      # noqa: E731
+    gamma, beta = d(1 + 0.1 * _rn(width, seed=4)), d(_rn(width, seed=5))
+    x = d(_rn(N * T, width, seed=9) * 2 + 3)
+    index = torch.tensor([0, T - 1, 2], dtype=torch.int32)
+    want, _ = ops.add_layernorm(d(x.view(N, T, width)[torch.arange(N), index.long()]), None, gamma, beta, 1e-5)
+    assert torch.equal(ops.clip_pool_ln(x, index.to(DEV), T, gamma, beta, 1e-5), want)
+
+    patch, cls, pos = d(_rn(N * GG, width, seed=1) + 2.0), d(_rn(width, seed=2)), d(_rn(GG + 1, width, seed=3))
+    rows = torch.cat([cls.expand(N, 1, width), patch.view(N, GG, width)], 1).reshape(N * (GG + 1), width).contiguous()
+    want, _ = ops.add_layernorm(rows, pos.repeat(N, 1), gamma, beta, 1e-5)
+    assert torch.equal(ops.clip_vision_embed(patch, cls, pos, gamma, beta, 1e-5), want)
+
+
 # ------------------------------------------------------------------------------------------ the towers
 TOWER_BAR = {("tiny", "image"): 1.5 * 1.080e-06, ("tiny", "text"): 1.5 * 1.242e-06, ("b32", "image"): 1.5 * 5.937e-06,
              ("b32", "text"): 1.5 * 3.548e-06}          # 1.5 x measured (tiny: the larger of the two activations)

@@ -322,7 +322,7 @@ def test_product_never_touches_the_oracle_or_a_cpu_fallback():
     assert "/root/reference" not in bench                                  # nothing at run time reads the reference
 
 
-OPS_LAYERS = ("_config", "_engine", "_nodes_leaf", "_nodes_conv", "_nodes_block", "_nodes_loss", "_functional")
+OPS_LAYERS = ("_config", "_engine", "_forward", "_nodes_leaf", "_nodes_conv", "_nodes_block", "_nodes_loss", "_functional")
 
 
 def test_ops_modules_import_only_from_earlier_layers():

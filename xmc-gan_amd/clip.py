@@ -15,31 +15,15 @@ import json
 import os
 
 import torch
-import torch.nn as nn
 
+from . import hfdir
 from . import lib as L
 from . import ops
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
-MAX_CONTEXT = 64              # the attention kernels' longest sequence
+MAX_CONTEXT = ops.ATTENTION_MAX_T              # the attention kernels' longest sequence
 _FILES = "config.json, model.safetensors or pytorch_model.bin, tokenizer.json [, preprocessor_config.json]"
-
-
-def _read_weights(model_dir):
-    st = os.path.join(model_dir, "model.safetensors")
-    if os.path.isfile(st):
-        try:
-            from safetensors.torch import load_file
-            return load_file(st)
-        except ImportError:
-            pass
-    pt = os.path.join(model_dir, "pytorch_model.bin")
-    if not os.path.isfile(pt):
-        what = "pytorch_model.bin (model.safetensors is there, but the safetensors package is not importable)" if os.path.isfile(st) \
-            else "model.safetensors / pytorch_model.bin"
-        raise ImportError(f"CLIPScorer: {model_dir} holds no {what}")
-    return torch.load(pt, map_location="cpu", weights_only=True)
 
 
 class _Tower:
@@ -57,7 +41,7 @@ class _Tower:
         W = self.width
         if self.heads * 64 != W:
             raise NotImplementedError(f"CLIPScorer: the kernels are built for head dimension 64; {name} has width {W} and {self.heads} heads")
-        if W % 64 or W > 1024 or self.ffn % 8:
+        if W % 64 or W > ops.LN_MAX_WIDTH or self.ffn % 8:
             raise NotImplementedError(f"CLIPScorer: the kernels are built for a width that is a multiple of 64 and <= 1024 and "
                                       f"intermediate_size % 8 == 0; {name} has width {W}, intermediate_size {self.ffn}")
         if self.act not in ("quick_gelu", "gelu"):
@@ -108,7 +92,7 @@ class CLIPScorer:
         self.image_batch = 256
         self._tokenizer = None
         self._read_preprocessor()
-        self._w = self._assemble(_read_weights(model_dir), cj)
+        self._w = self._assemble(hfdir.read_weights(model_dir, "CLIPScorer"), cj)
         self._lut = None
         self.g_patch = ops.ConvGeom(3 * self.patch * self.patch, self.vision.width, 1, 1, 0)
         self.g_vproj, self.g_tproj = ops.ConvGeom(self.vision.width, self.dim, 1, 1, 0), ops.ConvGeom(self.text.width, self.dim, 1, 1, 0)
@@ -134,18 +118,8 @@ class CLIPScorer:
     def _assemble(self, sd, cj):
         """the tensors the forwards read, as frozen f32 Parameters on the device (so that their packed copies are cached): q, k and v of a
         layer as one [3W, W] weight, the patch embedding as [W, 3 P P]"""
-        dev = self.device
         w = {}
-
-        def take(key, shape):
-            if key not in sd:
-                raise ImportError(f"CLIPScorer: the weights in {self.model_dir} lack {key!r}")
-            t = sd[key].detach().float()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"CLIPScorer: {key} is {tuple(t.shape)}, {cj} says {tuple(shape)}")
-            return t
-
-        frozen = lambda t: nn.Parameter(t.to(dev).contiguous(), requires_grad=False)      # noqa: E731
+        take, frozen = hfdir.weight_access(sd, "CLIPScorer", self.model_dir, cj, self.device)
         V, T, P = self.vision, self.text, self.patch
         v, t = "vision_model.", "text_model."
         w["v.cls"] = frozen(take(v + "embeddings.class_embedding", (V.width,)))
@@ -175,19 +149,9 @@ class CLIPScorer:
     # ------------------------------------------------------------------ host side: sentences -> token ids
     def tokenizer(self):
         if self._tokenizer is None:
-            try:
-                import tokenizers
-            except ImportError as e:
-                raise ImportError("CLIPScorer.tokenize uses the `tokenizers` package, which is not importable here; call "
-                                  "encode_text_ids(ids, lens) with ids tokenized elsewhere") from e
-            os.environ.setdefault("TOKENIZERS_PARALLELISM", "false")
-            tj = os.path.join(self.model_dir, "tokenizer.json")
-            if not os.path.isfile(tj):
-                raise ImportError(f"CLIPScorer: {self.model_dir} holds no tokenizer.json")
-            tok = tokenizers.Tokenizer.from_file(tj)
-            tok.no_truncation()
-            tok.no_padding()
-            self._tokenizer = tok
+            self._tokenizer = hfdir.load_tokenizer(
+                self.model_dir, "CLIPScorer", ("",), "CLIPScorer.tokenize uses the `tokenizers` package, which is not importable here; call "
+                "encode_text_ids(ids, lens) with ids tokenized elsewhere")
         return self._tokenizer
 
     def tokenize(self, sentences):

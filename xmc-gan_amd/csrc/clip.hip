@@ -1,23 +1,20 @@
 // CLIPScore (xmc_gan_amd/clip.py): what the two CLIP towers need besides the f32 GEMMs of the 1x1 convolution path and the
-// LayerNorm / short-sequence attention / erf-GELU kernels of transformer.hip.  Forward only, f32 in every build, no atomics anywhere:
+// LayerNorm / short-sequence attention / erf-GELU entry points of transformer.hip.  Forward only, f32 in every build, no atomics anywhere:
 // every output element has one writer and a fixed summation order, so the same inputs give the same bytes.
 //
 //   xmc_clip_resize_h_u8   Pillow's antialiased resize of an 8-bit image along x, bit for bit: int32 coefficients (22 fraction bits) and
 //   xmc_clip_resize_v_u8   bounds from the host, clip8((2^21 + sum pixel * k) >> 22); then the same along y, writing either the uint8
 //                          image or CLIP's input: centre crop, per-channel normalisation table, patch-major f32 rows
-//   xmc_attention_causal   softmax(Q K^T / sqrt(64)) V over keys j <= i per (sample, head), T <= 64 (attention_short's layout and schedule)
-//   xmc_bias_quick_gelu    v = x + bias; v * sigmoid(1.702 v), streaming in 8-element units
+//   xmc_attention_causal   softmax(Q K^T / sqrt(64)) V over keys j <= i per (sample, head), T <= 64 (encoder_kernels.h: attention_kernel<f32, causal>)
+//   xmc_bias_quick_gelu    v = x + bias; v * sigmoid(1.702 v), streaming in 8-element units (encoder_kernels.h: bias_act_kernel)
 //   xmc_clip_vision_embed  [class + pos[0] | patch[p] + pos[1 + p]] then LayerNorm: one wave per token row
 //   xmc_clip_text_embed    token[ids] + pos[t]: one wave per token row
 //   xmc_clip_pool_ln       LayerNorm of one row per sample, picked by an index
 //   xmc_clip_cosine        per image, the cosine of its feature row and its caption's: one wave per image
-#include "common.h"
+#include "encoder_kernels.h"
 
 namespace {
 
-constexpr int LN_MAXU = 4;          // 16-byte units per lane: rows of up to 64 * 4 * 4 = 1024 floats
-constexpr int AT_D = 64;            // head dimension
-constexpr int AT_T = 64;            // longest sequence
 constexpr int RS_NT = 256;
 
 __device__ __forceinline__ uint8_t clip8(int32_t acc) {
@@ -85,38 +82,6 @@ __global__ __launch_bounds__(RS_NT) void clip_resize_v_kernel(const uint8_t* __r
     }
 }
 
-// LayerNorm of the row a wave holds as v[k] = unit (lane + 64 k): f32 two-pass statistics, as transformer.hip's
-__device__ __forceinline__ void ln_row_store(f32x4 (&v)[LN_MAXU], int lane, int H4, int H, const f32x4* __restrict__ gamma,
-                                             const f32x4* __restrict__ beta, float eps, f32x4* __restrict__ out) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < LN_MAXU; ++k)
-        if (lane + 64 * k < H4) s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-    const float mean = wave_sum(s) / (float)H;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < LN_MAXU; ++k)
-        if (lane + 64 * k < H4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[k][i] -= mean;
-                q += v[k][i] * v[k][i];
-            }
-        }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)H + eps);
-#pragma unroll
-    for (int k = 0; k < LN_MAXU; ++k) {
-        const int u = lane + 64 * k;
-        if (u < H4) {
-            const f32x4 g = gamma[u], b = beta[u];
-            f32x4 y;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[i] = v[k][i] * rstd * g[i] + b[i];
-            out[u] = y;
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void clip_vision_embed_kernel(const f32x4* __restrict__ patch, const f32x4* __restrict__ cls,
                                                                 const f32x4* __restrict__ pos, const f32x4* __restrict__ gamma,
                                                                 const f32x4* __restrict__ beta, f32x4* __restrict__ out, int64_t rows,
@@ -134,7 +99,7 @@ __global__ __launch_bounds__(256) void clip_vision_embed_kernel(const f32x4* __r
             v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (u < H4) v[k] = a[u] + p[u];
         }
-        ln_row_store(v, lane, H4, H, gamma, beta, eps, out + row * H4);
+        ln_row_store(v, lane, H4, H, gamma, beta, eps, out + row * H4, nullptr);
     }
 }
 
@@ -166,62 +131,7 @@ __global__ __launch_bounds__(256) void clip_pool_ln_kernel(const f32x4* __restri
             v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (u < H4) v[k] = r[u];
         }
-        ln_row_store(v, lane, H4, H, gamma, beta, eps, out + (size_t)b * H4);
-    }
-}
-
-// one workgroup = one (sample, head); qkv rows are [Q (H) | K (H) | V (H)], head h in columns [64 h, 64 h + 64) of each
-__global__ __launch_bounds__(256) void attention_causal_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int H) {
-    extern __shared__ __attribute__((aligned(16))) float ac_smem[];
-    float (*q_s)[AT_D] = reinterpret_cast<float (*)[AT_D]>(ac_smem);                          // [T][64]
-    float (*v_s)[AT_D] = reinterpret_cast<float (*)[AT_D]>(ac_smem + (size_t)T * AT_D);       // [T][64]
-    float (*k_s)[AT_D + 1] = reinterpret_cast<float (*)[AT_D + 1]>(ac_smem + (size_t)2 * T * AT_D);   // [T][65]: the key on the lane
-    const int b = blockIdx.x, head = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* base = qkv + (size_t)b * T * 3 * H + head * AT_D;
-    for (int i = tid; i < T * (AT_D / 4); i += 256) {
-        const int t = i / (AT_D / 4), c = (i % (AT_D / 4)) * 4;
-        const float* r = base + (size_t)t * 3 * H + c;
-        const f32x4 q = *reinterpret_cast<const f32x4*>(r), k = *reinterpret_cast<const f32x4*>(r + H),
-                    v = *reinterpret_cast<const f32x4*>(r + 2 * H);
-        *reinterpret_cast<f32x4*>(&q_s[t][c]) = q;
-        *reinterpret_cast<f32x4*>(&v_s[t][c]) = v;
-        k_s[t][c] = k[0], k_s[t][c + 1] = k[1], k_s[t][c + 2] = k[2], k_s[t][c + 3] = k[3];
-    }
-    __syncthreads();
-    for (int r = wave; r < T; r += 4) {                       // (wave-uniform trip count and branches)
-        // scores: lane j holds key j; query r sees keys 0 .. r, so key 0 is always there and the row is finite
-        float s = 0.f;
-        if (lane <= r) {
-#pragma unroll
-            for (int d = 0; d < AT_D; d += 4) {
-                const f32x4 q = *reinterpret_cast<const f32x4*>(&q_s[r][d]);
-                s += q[0] * k_s[lane][d] + q[1] * k_s[lane][d + 1] + q[2] * k_s[lane][d + 2] + q[3] * k_s[lane][d + 3];
-            }
-            s *= 0.125f;                                      // 1 / sqrt(64)
-        }
-        const float m = wave_max(lane <= r ? s : -INFINITY);
-        const float p = lane <= r ? expf(s - m) : 0.f;
-        const float l = wave_sum(p);
-        // context: lane d holds channel d; p of key j comes out of lane j's register (j is wave-uniform)
-        float o = 0.f;
-        for (int j = 0; j <= r; ++j)
-            o += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, p), j)) * v_s[j][lane];
-        out[((size_t)b * T + r) * H + head * AT_D + lane] = o / l;
-    }
-}
-
-__global__ __launch_bounds__(256) void bias_quick_gelu_kernel(const float* __restrict__ x, const float* __restrict__ bias,
-                                                              float* __restrict__ out, int64_t n8, int F8) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-        float v[8], bv[8];
-        Vec8<XMC_F32>::load(x, (size_t)i, v);
-        Vec8<XMC_F32>::load(bias, (size_t)(i % F8), bv);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float a = v[k] + bv[k];
-            v[k] = a / (1.f + expf(-1.702f * a));             // a -> -inf: exp overflows to +inf and the quotient is -0, never a NaN
-        }
-        Vec8<XMC_F32>::store(out, (size_t)i, v);
+        ln_row_store(v, lane, H4, H, gamma, beta, eps, out + (size_t)b * H4, nullptr);
     }
 }
 
@@ -243,11 +153,7 @@ __global__ __launch_bounds__(256) void clip_cosine_kernel(const float* __restric
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline unsigned row_grid(int64_t rows) { return (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192); }
 inline unsigned px_grid(int64_t n) { return (unsigned)((n + RS_NT - 1) / RS_NT < 16384 ? (n + RS_NT - 1) / RS_NT : 16384); }
-inline bool ln_width(int H) { return H >= 64 && H % 64 == 0 && H <= 256 * LN_MAXU; }
 
 }  // namespace
 
@@ -292,9 +198,9 @@ extern "C" int xmc_attention_causal(const float* qkv, float* out, int B, int T, 
     if (B < 1 || heads < 1 || heads > 65535 || T < 1 || T > AT_T || head_dim != AT_D) return XMC_ESHAPE;    // other shapes are not built
     if (!aligned16(qkv) || !aligned4(out)) return XMC_EALIGN;
     const size_t lds = (size_t)T * (3 * AT_D + 1) * sizeof(float);            // <= 49408 bytes at T = 64
-    hipLaunchKernelGGL(attention_causal_kernel, dim3((unsigned)B, (unsigned)heads), dim3(256), lds, (hipStream_t)stream, qkv, out, T,
-                       heads * AT_D);
-    xmc_note_kernel("attention_causal_kernel");
+    hipLaunchKernelGGL((attention_kernel<XMC_F32, true>), dim3((unsigned)B, (unsigned)heads), dim3(256), lds, (hipStream_t)stream, qkv,
+                       (const int32_t*)nullptr, (void*)out, T, heads * AT_D);
+    xmc_note_kernel("attention_kernel<f32,true>");
     XMC_LAUNCH_CHECK();
     return 0;
 }
@@ -305,8 +211,9 @@ extern "C" int xmc_bias_quick_gelu(const float* x, const float* bias, float* out
     if (F % 8 || !aligned16(x) || !aligned16(bias) || !aligned16(out)) return XMC_EALIGN;
     const int64_t n8 = rows * (F / 8);
     const unsigned grid = (unsigned)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384);
-    hipLaunchKernelGGL(bias_quick_gelu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, bias, out, n8, F / 8);
-    xmc_note_kernel("bias_quick_gelu_kernel");
+    hipLaunchKernelGGL((bias_act_kernel<XMC_F32, ACT_QUICK_GELU>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, bias, (void*)out, n8,
+                       F / 8);
+    xmc_note_kernel("bias_act_kernel<f32,%d>", ACT_QUICK_GELU);
     XMC_LAUNCH_CHECK();
     return 0;
 }

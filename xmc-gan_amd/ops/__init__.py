@@ -11,9 +11,9 @@ PyTorch is used for storage, streams and the autograd graph only.
 The modules are layers: each imports only from those before it in the tuple below.
 """
 from types import ModuleType
-from . import _config, _engine, _nodes_leaf, _nodes_conv, _nodes_block, _nodes_loss, _functional
+from . import _config, _engine, _forward, _nodes_leaf, _nodes_conv, _nodes_block, _nodes_loss, _functional
 
 # the public (and test-visible) surface: everything the modules define, under its own name
-for _m in (_config, _engine, _nodes_leaf, _nodes_conv, _nodes_block, _nodes_loss, _functional):
+for _m in (_config, _engine, _forward, _nodes_leaf, _nodes_conv, _nodes_block, _nodes_loss, _functional):
     globals().update({_k: _v for _k, _v in vars(_m).items() if not _k.startswith("__") and not isinstance(_v, ModuleType)})
 del _m, ModuleType

@@ -1,4 +1,4 @@
-"""xmc_gan_amd.ops, layer 7 (the last): one-line functional wrappers over the nodes.  May import every other module of the package."""
+"""xmc_gan_amd.ops, layer 8 (the last): one-line functional wrappers over the nodes.  May import every other module of the package."""
 import torch
 from ._config import act_dtype
 from ._nodes_leaf import AxpbyFn, AxpbyUpFn, CastFn, DiffAugFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, SumPool2Fn, Up2Fn

@@ -1,4 +1,4 @@
-"""xmc_gan_amd.ops, layer 5: the discriminator blocks (first- and second-order) and the nodes of affine modulation, GroupNorm /
+"""xmc_gan_amd.ops, layer 6: the discriminator blocks (first- and second-order) and the nodes of affine modulation, GroupNorm /
 BatchNorm and region attention.  Imports `_config`, `_engine`, `_nodes_leaf` and `_nodes_conv`."""
 import torch
 from .. import lib as L

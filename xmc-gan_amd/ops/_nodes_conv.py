@@ -1,7 +1,6 @@
-"""xmc_gan_amd.ops, layer 4: autograd nodes of the convolution / linear layers, the generator block end, the conditioning-MLP bank
-and the text front end.  Imports `_config`, `_engine` and `_nodes_leaf`."""
+"""xmc_gan_amd.ops, layer 5: autograd nodes of the convolution / linear layers, the generator block end, the conditioning-MLP bank
+and spectral normalisation.  Imports `_config`, `_engine` and `_nodes_leaf`."""
 import ctypes as C
-import math
 import numpy as np
 import torch
 from .. import lib as L
@@ -488,329 +487,7 @@ def cond_mlp_bank(c, mlps):
     return CondMLPBankFn.apply(c.float(), *flat)
 
 
-# ------------------------------------------------------------------------------------------ text front end
-def embedding(ids, table):
-    """nn.Embedding lookup (encoder.py:132), forward only (the encoder is frozen, train_gan.py:466-468).
-    ids: int64 [...] on the device; table f32 [V, D] with D % 4 == 0.  Returns f32 [..., D]."""
-    if not table.is_cuda or not ids.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.embedding: CPU tensors are not supported (no CPU fallback)")
-    assert ids.dtype == torch.int64 and table.dtype == torch.float32 and table.dim() == 2
-    ids = ids.contiguous()
-    table = table.detach().contiguous()
-    out = torch.empty(*ids.shape, table.shape[1], dtype=torch.float32, device=table.device)
-    L.call("xmc_embedding_gather", _p(ids), _p(table), _p(out), ids.numel(), table.shape[1], table.shape[0], _st())
-    return out
-
-
-def lstm_bidir(xproj, w_hh, lens, T):
-    """One-layer bidirectional LSTM recurrence over length-packed sequences (encoder.py:134-147), forward only.
-    xproj f32 [B,T,2,4H] (input projections + both biases), w_hh f32 [2,4H,H], lens int32 [B].
-    Returns words [B,2H,T] (zero at t >= len) and sent [B,2H] = [h_fwd(len-1), h_rev(0)]."""
-    if not xproj.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.lstm_bidir: CPU tensors are not supported (no CPU fallback)")
-    B, H = xproj.shape[0], w_hh.shape[2]
-    assert xproj.dtype == torch.float32 and xproj.is_contiguous() and xproj.shape == (B, T, 2, 4 * H)
-    assert w_hh.dtype == torch.float32 and w_hh.is_contiguous() and w_hh.shape == (2, 4 * H, H)
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
-    words = torch.empty(B, 2 * H, T, dtype=torch.float32, device=xproj.device)
-    sent = torch.empty(B, 2 * H, dtype=torch.float32, device=xproj.device)
-    L.call("xmc_lstm_bidir", _p(xproj), _p(w_hh), _p(lens), _p(words), _p(sent), B, T, H, _st())
-    return words, sent
-
-
-def gru_bidir(xproj, w_hh, b_hn, lens, T):
-    """One-layer bidirectional GRU recurrence over length-packed sequences (encoder.py:99-102,134-147 with RNN_TYPE 'GRU'),
-    forward only.  xproj f32 [B,T,2,3H] (W_i* x + b_i*, plus b_h* for the r and z rows), w_hh f32 [2,3H,H], b_hn f32 [2,H],
-    lens int32 [B].  Returns words [B,2H,T] (zero at t >= len) and sent [B,2H] = [h_fwd(len-1), h_rev(0)]."""
-    if not xproj.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.gru_bidir: CPU tensors are not supported (no CPU fallback)")
-    B, H = xproj.shape[0], w_hh.shape[2]
-    assert xproj.dtype == torch.float32 and xproj.is_contiguous() and xproj.shape == (B, T, 2, 3 * H)
-    assert w_hh.dtype == torch.float32 and w_hh.is_contiguous() and w_hh.shape == (2, 3 * H, H)
-    assert b_hn.dtype == torch.float32 and b_hn.is_contiguous() and b_hn.shape == (2, H)
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
-    words = torch.empty(B, 2 * H, T, dtype=torch.float32, device=xproj.device)
-    sent = torch.empty(B, 2 * H, dtype=torch.float32, device=xproj.device)
-    L.call("xmc_gru_bidir", _p(xproj), _p(w_hh), _p(b_hn), _p(lens), _p(words), _p(sent), B, T, H, _st())
-    return words, sent
-
-
-# sentence encoder (SBERT_ENCODER: a frozen RoBERTa forward; csrc/transformer.hip).  Forward only, like the RNN front end above; the GEMMs
-# between these go through `linear`.  `out16`: also return the result in that 16-bit dtype (the next GEMM's operand), None in fp32 mode.
-def _enc_f32c(*ts):
-    for t in ts:
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "f32 contiguous tensors expected"
-
-
-def _enc_out16(like, out16):
-    assert out16 in (None, torch.float32) or _code(out16) == L.H16
-    return None if out16 in (None, torch.float32) else torch.empty_like(like, dtype=out16)
-
-
-def roberta_embed_ln(ids, lens, word, pos, type0, gamma, beta, eps, pad_idx, out16=None):
-    """RobertaEmbeddings: LN(word[ids] + token_type[0] + position[p]) with p = cumsum(mask) * mask + pad_idx computed in the kernel from
-    the lengths of the right-padded batch.  ids int64 [B,T], lens int32 [B]; word [V,H], pos [P,H], type0 [H].
-    Returns f32 [B*T,H] (and its 16-bit copy when `out16` names one, else None)."""
-    if not ids.is_cuda or not word.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.roberta_embed_ln: CPU tensors are not supported (no CPU fallback)")
-    B, T = ids.shape
-    H = word.shape[1]
-    assert ids.dtype == torch.int64 and ids.is_contiguous() and lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
-    _enc_f32c(word, pos, type0, gamma, beta)
-    assert pos.shape[1] == H and type0.numel() == H and gamma.numel() == H and beta.numel() == H
-    out = torch.empty(B * T, H, dtype=torch.float32, device=word.device)
-    o16 = _enc_out16(out, out16)
-    L.call("xmc_roberta_embed_ln", _p(ids), _p(lens), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), _p(out), _p(o16), B, T, H,
-           word.shape[0], pos.shape[0], int(pad_idx), float(eps), _st())
-    return out, o16
-
-
-def add_layernorm(x, res, gamma, beta, eps, bias=None, out16=None):
-    """LN(x [+ bias] [+ res]) * gamma + beta over the last dimension of f32 [rows,H] (H a multiple of 64, <= 1024): one wave per row, f32
-    two-pass statistics.  Returns f32 [rows,H] and its 16-bit copy (None unless `out16` names a 16-bit dtype)."""
-    if not x.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.add_layernorm: CPU tensors are not supported (no CPU fallback)")
-    rows, H = x.shape
-    _enc_f32c(x, res, gamma, beta, bias)
-    assert res is None or res.shape == x.shape
-    assert gamma.numel() == H and beta.numel() == H and (bias is None or bias.numel() == H)
-    out = torch.empty_like(x)
-    o16 = _enc_out16(out, out16)
-    L.call("xmc_add_layernorm", _p(x), _p(bias), _p(res), _p(gamma), _p(beta), _p(out), _p(o16), rows, H, float(eps), _st())
-    return out, o16
-
-
-def attention_short(qkv, lens, B, T, heads, out_dtype=torch.float32):
-    """softmax(Q K^T / sqrt(d) + key padding mask) V per (sample, head) from the fused QKV projection f32 [B*T,3H] (rows [Q | K | V]), for
-    head dimension 64 and T <= 64; the scores never reach memory.  Rows of padded queries come back as zeros.  Returns [B*T,H]."""
-    if not qkv.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.attention_short: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(qkv)
-    assert qkv.dim() == 2 and qkv.shape[0] == B * T and qkv.shape[1] % (3 * heads) == 0
-    d = qkv.shape[1] // (3 * heads)
-    assert d == 64 and 1 <= T <= 64, f"attention_short is built for head dimension 64 and T <= 64, got d={d}, T={T}"
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
-    out = torch.empty(B * T, heads * d, dtype=out_dtype, device=qkv.device)
-    L.call("xmc_attention_short", _p(qkv), _p(lens), _p(out), B, T, heads, d, _code(out_dtype), _st())
-    return out
-
-
-def bias_gelu(x, bias, out_dtype=torch.float32):
-    """gelu(x + bias) with the exact (erf) GELU -- Hugging Face's hidden_act "gelu" -- over f32 [rows,F], F % 8 == 0."""
-    if not x.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.bias_gelu: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(x, bias)
-    assert x.dim() == 2 and bias.numel() == x.shape[1]
-    out = torch.empty_like(x, dtype=out_dtype)
-    L.call("xmc_bias_gelu", _p(x), _p(bias), _p(out), x.shape[0], x.shape[1], _code(out_dtype), _st())
-    return out
-
-
-def sbert_pool(hidden, lens, max_length, normalize):
-    """The tail of SBERT_ENCODER.forward (encoder.py:50-70) in one launch.  hidden f32 [B,T,H], lens int32 [B], T <= max_length <= 64.
-    Returns words_embs [B,H,max_length] (token embeddings x attention mask, zero at padding and beyond T), sent_embs [B,H] (mean over the
-    valid tokens, L2-normalised when `normalize`) and mask bool [B,max_length] (True at padding)."""
-    if not hidden.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.sbert_pool: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(hidden)
-    B, T, H = hidden.shape
-    assert T <= max_length <= 64, f"sbert_pool is built for T <= max_length <= 64, got T={T}, max_length={max_length}"
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B
-    words = torch.empty(B, H, max_length, dtype=torch.float32, device=hidden.device)
-    sent = torch.empty(B, H, dtype=torch.float32, device=hidden.device)
-    mask = torch.empty(B, max_length, dtype=torch.bool, device=hidden.device)
-    L.call("xmc_sbert_pool", _p(hidden), _p(lens), _p(words), _p(sent), _p(mask), B, T, H, max_length, int(bool(normalize)), _st())
-    return words, sent, mask
-
-
-# CLIPScore (xmc_gan_amd.clip: the CLIP ViT-B/32 towers; csrc/clip.hip).  Forward only and f32 in every precision mode; the GEMMs between
-# these go through `_conv_fwd_raw`, whose epilogue adds the bias and the residual.
-_pil_tables = {}          # (in, out) -> (bounds, coeffs, ksize) on the host;  (in, out, device) -> the same as int32 device tensors
-
-
-def _pil_cubic(x):
-    """Pillow's bicubic_filter: the Keys cubic with a = -0.5"""
-    x = -x if x < 0.0 else x
-    if x < 1.0:
-        return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * -0.5
-    return 0.0
-
-
-def pil_bicubic_tables(n_in, n_out):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c) for one axis of ``n_in`` -> ``n_out`` samples, in f64 in Pillow's
-    order of operations: (bounds [(first sample, count)] * n_out, coeffs [[int] * ksize] * n_out, ksize).  The weights carry 22 fraction
-    bits; refuses a table whose worst case 255 * sum |k| + 2^21 does not fit the kernels' int32 accumulator."""
-    key = (int(n_in), int(n_out))
-    if key not in _pil_tables:
-        n_in, n_out = key
-        assert n_in >= 1 and n_out >= 1
-        scale = n_in / n_out
-        fscale = scale if scale > 1.0 else 1.0
-        support = 2.0 * fscale
-        ksize = int(math.ceil(support)) * 2 + 1
-        ss = 1.0 / fscale
-        bounds, coeffs = [], []
-        for xx in range(n_out):
-            center = 0.0 + (xx + 0.5) * scale
-            xmin = max(int(center - support + 0.5), 0)
-            xmax = min(int(center + support + 0.5), n_in) - xmin
-            w = [_pil_cubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
-            ww = 0.0
-            for v in w:
-                ww += v
-            if ww != 0.0:
-                w = [v / ww for v in w]
-            k = [int(-0.5 + v * 4194304.0) if v < 0 else int(0.5 + v * 4194304.0) for v in w] + [0] * (ksize - xmax)
-            if 255 * sum(abs(v) for v in k) + (1 << 21) >= 1 << 31:
-                raise ValueError(f"resize_bicubic_u8: the {n_in} -> {n_out} filter overflows the int32 accumulator")
-            bounds.append((xmin, xmax))
-            coeffs.append(k)
-        _pil_tables[key] = (bounds, coeffs, ksize)
-    return _pil_tables[key]
-
-
-def _pil_tables_dev(n_in, n_out, device):
-    key = (int(n_in), int(n_out), str(device))
-    if key not in _pil_tables:
-        bounds, coeffs, ksize = pil_bicubic_tables(n_in, n_out)
-        _pil_tables[key] = (torch.tensor(bounds, dtype=torch.int32).to(device).contiguous(),
-                            torch.tensor(coeffs, dtype=torch.int32).to(device).contiguous(), ksize)
-    return _pil_tables[key]
-
-
-def _resize_u8_h(u8, ow):
-    """the horizontal pass into uint8 [N,H,ow,3] (Pillow skips a pass that changes nothing; an identity filter gives the same bytes)"""
-    if not u8.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.resize_bicubic_u8: CPU tensors are not supported (no CPU fallback)")
-    assert u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3 and u8.is_contiguous(), "uint8 [N,H,W,3] expected"
-    N, H, W, _ = u8.shape
-    if ow == W:
-        return u8
-    bw, cw, kw = _pil_tables_dev(W, ow, u8.device)
-    mid = torch.empty(N, H, ow, 3, dtype=torch.uint8, device=u8.device)
-    L.call("xmc_clip_resize_h_u8", _p(u8), _p(mid), _p(bw), _p(cw), N, H, W, ow, kw, _st())
-    return mid
-
-
-def resize_bicubic_u8(u8, oh, ow):
-    """``PIL.Image.resize((ow, oh), BICUBIC)`` of uint8 [N,H,W,3] images, bit for bit: Pillow's antialiased two-pass integer resampling
-    (horizontal into uint8, then vertical), with the coefficient tables computed on the host in f64.  Returns uint8 [N,oh,ow,3]."""
-    mid = _resize_u8_h(u8, ow)
-    N, H = mid.shape[:2]
-    bh, ch, kh = _pil_tables_dev(H, oh, mid.device)
-    out = torch.empty(N, oh, ow, 3, dtype=torch.uint8, device=mid.device)
-    L.call("xmc_clip_resize_v_u8", _p(mid), _p(out), _p(bh), _p(ch), None, N, H, ow, oh, kh, 0, 0, 1, 0, 0, _st())
-    return out
-
-
-def clip_resize_target(h, w, short):
-    """CLIP's resize: the short side to ``short``, the long side to int(short * long / short side)"""
-    return (short, int(short * w / h)) if h <= w else (int(short * h / w), short)
-
-
-def clip_patch_rows(u8, short, crop, patch, lut):
-    """CLIP's image preprocessing in two launches: resize (short side ``short``, `resize_bicubic_u8`'s arithmetic), centre crop
-    ``crop`` x ``crop``, per-channel normalisation through ``lut`` f32 [3,256], written as the patch embedding's GEMM operand
-    f32 [N*(crop/patch)^2, 3*patch*patch] (column c*patch^2 + py*patch + px: the flatten order of ``patch_embedding.weight``)."""
-    N, H, W, _ = u8.shape
-    oh, ow = clip_resize_target(H, W, short)
-    assert crop % patch == 0 and crop <= min(oh, ow), f"a {crop}-pixel crop of a {oh}x{ow} image in {patch}-pixel patches is not built"
-    _enc_f32c(lut)
-    assert tuple(lut.shape) == (3, 256)
-    mid = _resize_u8_h(u8, ow)
-    bh, ch, kh = _pil_tables_dev(H, oh, mid.device)
-    g = crop // patch
-    out = torch.empty(N * g * g, 3 * patch * patch, dtype=torch.float32, device=mid.device)
-    L.call("xmc_clip_resize_v_u8", _p(mid), _p(out), _p(bh), _p(ch), _p(lut), N, H, ow, oh, kh, 1, crop, patch, (oh - crop) // 2,
-           (ow - crop) // 2, _st())
-    return out
-
-
-def attention_causal(qkv, B, T, heads):
-    """`attention_short` over keys j <= i (CLIP's text tower): qkv f32 [B*T,3H], head dimension 64, T <= 64.  Returns f32 [B*T,H]."""
-    if not qkv.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.attention_causal: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(qkv)
-    assert qkv.dim() == 2 and qkv.shape[0] == B * T and qkv.shape[1] % (3 * heads) == 0
-    d = qkv.shape[1] // (3 * heads)
-    assert d == 64 and 1 <= T <= 64, f"attention_causal is built for head dimension 64 and T <= 64, got d={d}, T={T}"
-    out = torch.empty(B * T, heads * d, dtype=torch.float32, device=qkv.device)
-    L.call("xmc_attention_causal", _p(qkv), _p(out), B, T, heads, d, _st())
-    return out
-
-
-def bias_quick_gelu(x, bias):
-    """v * sigmoid(1.702 v), v = x + bias -- Hugging Face's hidden_act "quick_gelu" -- over f32 [rows,F], F % 8 == 0."""
-    if not x.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.bias_quick_gelu: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(x, bias)
-    assert x.dim() == 2 and bias.numel() == x.shape[1]
-    out = torch.empty_like(x)
-    L.call("xmc_bias_quick_gelu", _p(x), _p(bias), _p(out), x.shape[0], x.shape[1], _st())
-    return out
-
-
-def clip_vision_embed(patch, cls, pos, gamma, beta, eps):
-    """CLIPVisionEmbeddings + pre_layrnorm: rows [class + pos[0] | patch[p] + pos[1 + p]] of every image, then LayerNorm.
-    patch f32 [N*GG,W], cls [W], pos [GG+1,W].  Returns f32 [N*(GG+1),W]."""
-    if not patch.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.clip_vision_embed: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(patch, cls, pos, gamma, beta)
-    GG, W = pos.shape[0] - 1, pos.shape[1]
-    assert patch.dim() == 2 and patch.shape[1] == W and GG >= 1 and patch.shape[0] % GG == 0
-    assert cls.numel() == W and gamma.numel() == W and beta.numel() == W
-    N = patch.shape[0] // GG
-    out = torch.empty(N * (GG + 1), W, dtype=torch.float32, device=patch.device)
-    L.call("xmc_clip_vision_embed", _p(patch), _p(cls), _p(pos), _p(gamma), _p(beta), _p(out), N, GG, W, float(eps), _st())
-    return out
-
-
-def clip_text_embed(ids, tok, pos):
-    """CLIPTextEmbeddings: tok[ids] + pos[t].  ids int64 [B,T] on the device, tok [V,W], pos [P,W] with T <= P.  Returns f32 [B*T,W]."""
-    if not ids.is_cuda or not tok.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.clip_text_embed: CPU tensors are not supported (no CPU fallback)")
-    B, T = ids.shape
-    assert ids.dtype == torch.int64 and ids.is_contiguous()
-    _enc_f32c(tok, pos)
-    assert pos.shape[1] == tok.shape[1] and T <= pos.shape[0]
-    out = torch.empty(B * T, tok.shape[1], dtype=torch.float32, device=tok.device)
-    L.call("xmc_clip_text_embed", _p(ids), _p(tok), _p(pos), _p(out), B, T, tok.shape[1], tok.shape[0], pos.shape[0], _st())
-    return out
-
-
-def clip_pool_ln(x, index, T, gamma, beta, eps):
-    """LayerNorm of row index[b] of every sample of x f32 [B*T,W]; index int32 [B].  Returns f32 [B,W]."""
-    if not x.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.clip_pool_ln: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(x, gamma, beta)
-    B, W = index.numel(), x.shape[1]
-    assert x.dim() == 2 and x.shape[0] == B * T and index.dtype == torch.int32 and index.is_contiguous()
-    assert gamma.numel() == W and beta.numel() == W
-    out = torch.empty(B, W, dtype=torch.float32, device=x.device)
-    L.call("xmc_clip_pool_ln", _p(x), _p(index), _p(gamma), _p(beta), _p(out), B, T, W, float(eps), _st())
-    return out
-
-
-def clip_cosine(img, txt, caption_of_image=None):
-    """per image, the cosine of its feature row img [N,D] and the row of its caption in txt [M,D]: row caption_of_image[n] (int32 [N]),
-    or row n.  One wave per image, a fixed summation order.  Returns f32 [N]."""
-    if not img.is_cuda or not txt.is_cuda:
-        raise RuntimeError("xmc_gan_amd.ops.clip_cosine: CPU tensors are not supported (no CPU fallback)")
-    _enc_f32c(img, txt)
-    N, D = img.shape
-    M = txt.shape[0]
-    assert txt.shape[1] == D
-    if caption_of_image is None:
-        assert N <= M, "without caption_of_image every image needs a caption row of its own"
-    else:
-        assert caption_of_image.dtype == torch.int32 and caption_of_image.is_contiguous() and caption_of_image.numel() == N
-    out = torch.empty(N, dtype=torch.float32, device=img.device)
-    L.call("xmc_clip_cosine", _p(img), _p(txt), _p(caption_of_image), _p(out), N, M, D, _st())
-    return out
-
-
+# ------------------------------------------------------------------------------------------ spectral norm
 class SpectralNormFn(torch.autograd.Function):
     """W / sigma(W) as the legacy ``torch.nn.utils.spectral_norm`` hook computes it (reference model/modules.py:3,16-17,
     31-32): in training mode ONE power iteration updates ``u`` [R] / ``v`` [C] in place (v <- normalize(W^T u),

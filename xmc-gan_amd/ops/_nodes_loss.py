@@ -1,4 +1,4 @@
-"""xmc_gan_amd.ops, layer 6: losses (hinge, contrastive head), the concept algebra of the attention-modulation and word-attention
+"""xmc_gan_amd.ops, layer 7: losses (hinge, contrastive head), the concept algebra of the attention-modulation and word-attention
 generators, the gradient penalty.  Imports `_config`, `_engine`, `_nodes_conv` and `_nodes_block`."""
 import ctypes as C
 import numpy as np

@@ -24,6 +24,7 @@ import os
 import torch
 import torch.nn as nn
 
+from xmc_gan_amd import hfdir
 from xmc_gan_amd import lib as _L
 from xmc_gan_amd import ops
 
@@ -110,32 +111,9 @@ _SBERT_SUBDIRS = ("", "0_Transformer")          # the directory itself; the olde
 _SBERT_DROP = ("pooler.", "lm_head.", "classifier.", "embeddings.position_ids")
 
 
-def _sbert_find(model_dir, names):
-    for sub in _SBERT_SUBDIRS:
-        for n in names:
-            p = os.path.join(model_dir, sub, n)
-            if os.path.isfile(p):
-                return p
-    return None
-
-
 def _sbert_read_weights(model_dir):
     """{Hugging Face key without the 'roberta.' prefix: tensor}; pooler / LM head keys dropped"""
-    st = _sbert_find(model_dir, ("model.safetensors",))
-    sd = None
-    if st is not None:
-        try:
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        except ImportError:
-            sd = None
-    if sd is None:
-        pt = _sbert_find(model_dir, ("pytorch_model.bin",))
-        if pt is None:
-            what = "pytorch_model.bin (model.safetensors is there, but the safetensors package is not importable)" if st \
-                else "model.safetensors / pytorch_model.bin"
-            raise ImportError(f"SBERT_ENCODER: {model_dir} holds no {what} (looked in the directory and in 0_Transformer/)")
-        sd = torch.load(pt, map_location="cpu", weights_only=True)
+    sd = hfdir.read_weights(model_dir, "SBERT_ENCODER", _SBERT_SUBDIRS, " (looked in the directory and in 0_Transformer/)")
     out = {}
     for k, v in sd.items():
         k = k[len("roberta."):] if k.startswith("roberta.") else k
@@ -163,7 +141,7 @@ class SBERT_ENCODER(nn.Module):
                 "set XMC_SBERT_DIR.  None is given.  Use a TEXT.ENCODER_NAME: 'RNN' preset or --synthetic otherwise.")
         if not os.path.isdir(model_dir):
             raise ImportError(f"SBERT_ENCODER: the model directory {model_dir} does not exist")
-        cj = _sbert_find(model_dir, ("config.json",))
+        cj = hfdir.find(model_dir, ("config.json",), _SBERT_SUBDIRS)
         if cj is None:
             raise ImportError(f"SBERT_ENCODER: {model_dir} holds no config.json (looked in the directory and in 0_Transformer/)")
         with open(cj) as f:
@@ -184,7 +162,7 @@ class SBERT_ENCODER(nn.Module):
         self.vocab, self.npos = int(hf["vocab_size"]), int(hf["max_position_embeddings"])
         if H != cfg.TEXT.EMBEDDING_DIM:
             raise ValueError(f"SBERT_ENCODER: {cj} has hidden_size {H}, the preset's TEXT.EMBEDDING_DIM is {cfg.TEXT.EMBEDDING_DIM}")
-        if self.heads * 64 != H or H > 1024 or self.ffn % 8 or self.max_seq_length > 64:
+        if self.heads * 64 != H or H > ops.LN_MAX_WIDTH or self.ffn % 8 or self.max_seq_length > ops.ATTENTION_MAX_T:
             raise NotImplementedError(f"SBERT_ENCODER: the kernels are built for head dimension 64, hidden_size <= 1024, intermediate_size % 8 "
                                       f"== 0 and TEXT.MAX_LENGTH <= 64 (got hidden {H}, {self.heads} heads, FFN {self.ffn}, MAX_LENGTH {self.max_seq_length})")
         if self.max_seq_length + self.pad_id + 1 > self.npos:
@@ -201,16 +179,7 @@ class SBERT_ENCODER(nn.Module):
         Q, K, V of a layer as one [3H, H] weight"""
         H, F = self.hidden, self.ffn
         w = {}
-
-        def take(key, shape):
-            if key not in sd:
-                raise ImportError(f"SBERT_ENCODER: the weights in {self.model_dir} lack {key!r}")
-            t = sd[key].detach().float().contiguous()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"SBERT_ENCODER: {key} is {tuple(t.shape)}, {cj} says {tuple(shape)}")
-            return t
-
-        frozen = lambda t: nn.Parameter(t.contiguous(), requires_grad=False)
+        take, frozen = hfdir.weight_access(sd, "SBERT_ENCODER", self.model_dir, cj)
         e = "embeddings."
         w["word"] = frozen(take(e + "word_embeddings.weight", (self.vocab, H)))
         w["pos"] = frozen(take(e + "position_embeddings.weight", (self.npos, H)))
@@ -247,24 +216,10 @@ class SBERT_ENCODER(nn.Module):
         """the directory's byte-level BPE through the `tokenizers` package (tokenizer.json, or vocab.json + merges.txt), without its own
         truncation, padding or special tokens: `tokenize` adds those"""
         if self._tokenizer is None:
-            try:
-                import tokenizers
-            except ImportError as e:
-                raise ImportError("SBERT_ENCODER.forward tokenizes with the `tokenizers` package, which is not importable here; "
-                                  "call forward_ids(input_ids, lengths) with ids tokenized elsewhere") from e
-            os.environ.setdefault('TOKENIZERS_PARALLELISM', 'false')           # encoder.py:28
-            tj = _sbert_find(self.model_dir, ("tokenizer.json",))
-            if tj is not None:
-                tok = tokenizers.Tokenizer.from_file(tj)
-            else:
-                vj, mt = _sbert_find(self.model_dir, ("vocab.json",)), _sbert_find(self.model_dir, ("merges.txt",))
-                if vj is None or mt is None:
-                    raise ImportError(f"SBERT_ENCODER: {self.model_dir} holds neither tokenizer.json nor vocab.json + merges.txt")
-                tok = tokenizers.Tokenizer(tokenizers.models.BPE.from_file(vj, mt))         # RoBERTa's: byte-level, no prefix space
-                tok.pre_tokenizer = tokenizers.pre_tokenizers.ByteLevel(add_prefix_space=False)
-            tok.no_truncation()
-            tok.no_padding()
-            self._tokenizer = tok
+            self._tokenizer = hfdir.load_tokenizer(      # (TOKENIZERS_PARALLELISM=false as in encoder.py:28)
+                self.model_dir, "SBERT_ENCODER", _SBERT_SUBDIRS,
+                "SBERT_ENCODER.forward tokenizes with the `tokenizers` package, which is not importable here; "
+                "call forward_ids(input_ids, lengths) with ids tokenized elsewhere", bpe_files=True)
         return self._tokenizer
 
     def tokenize(self, sents):
