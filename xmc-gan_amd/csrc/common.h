@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "xmc_gan_hip.h"
 
@@ -64,6 +65,19 @@ hipError_t xmc_zero_acc(void* p, size_t bytes, hipStream_t st);      // memset u
             once__ = true;                                                                                                     \
         }                                                                                                                      \
     } while (0)
+
+// The launch protocol of the convolution launchers, in this order: raise the kernel's dynamic-LDS limit (BIG_LDS; once per instantiation),
+// launch, record the name for xmc_last_kernel (the format and its %d arguments, as xmc_note_kernel takes them), check the launch.
+// Returns 0 or the launch check's -(1000 + hipError).
+struct XmcKName { const char* fmt; int a[6]; };
+template <auto KERNEL, bool BIG_LDS = true, typename... Args>
+static inline int xmc_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const XmcKName& name, const Args&... args) {
+    if (BIG_LDS) XMC_ALLOW_BIG_LDS(*KERNEL);
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+    xmc_note_kernel(name.fmt, name.a[0], name.a[1], name.a[2], name.a[3], name.a[4], name.a[5]);
+    XMC_LAUNCH_CHECK();
+    return 0;
+}
 
 // ds_read_b64_tr_b16 (transposing LDS read of four 16-bit elements), format-agnostic through the i16 form of the builtin
 __device__ __forceinline__ bf16x4 xmc_ds_read_tr16(const void* p) {
@@ -278,6 +292,31 @@ static inline int xmc_epi_mask(const XmcConvDesc& d) {
     return (d.bias ? kEpiBias : 0) | (d.act == XMC_ACT_LRELU ? kEpiLrelu : 0) | ((d.round_act && !d.dst2) ? kEpiRound : 0) | (d.dst2 ? kEpiDst2 : 0) |
            (d.alpha_dev ? kEpiAlpha : 0) | (d.mask ? kEpiMask : 0) | (d.res ? kEpiRes : 0) | (d.post_act == XMC_ACT_LRELU ? kEpiPost : 0) |
            (d.dst_pool ? kEpiPool : 0) | (d.sign_bits ? kEpiSign : 0) | (d.dot ? kEpiDot : 0) | (d.sc_img ? kEpiScImg : 0);
+}
+
+// Which sets get an instantiation, per kernel family: THE table.  A launcher offers its family's list to xmc_epi_launch and sends
+// everything else through its descriptor-reading instantiation (xmc_note_generic_epi says so), so a set that joins the training step
+// is added here, once per family that should carry it.
+template <int... E> struct XmcEpiList {};
+template <int... A, int... B> constexpr XmcEpiList<A..., B...> operator+(XmcEpiList<A...>, XmcEpiList<B...>) { return {}; }
+// the block-end sets (+ the data gradient through a LeakyReLU): ptile3's 32x32x16 role, wtile2<9, 0, 8> and wtile3<9, 0>
+constexpr XmcEpiList<kEpiGSum, kEpiDKeep, kEpiDFwd, kEpiDLast, kEpiDLin, kEpiDKeepS, kEpiDLastS, kEpiDgDot, kEpiMask> kEpiBlockEnd{};
+// ... with the residual recomputed from the image (xmc_conv_ptile_scimg)
+constexpr XmcEpiList<(kEpiDKeepS & ~kEpiRes) | kEpiScImg, (kEpiDFwd & ~kEpiRes) | kEpiScImg> kEpiBlockEndScImg{};
+// 4x4 stride 2: forward; data gradient of the fused upsample conv; MA-GP's linearised forward
+constexpr XmcEpiList<kEpiLrelu, 0, kEpiMask> kEpiStride2{};
+// 2x2 tap classes (the data gradient of a 4x4 stride-2 layer, the fused upsample + 3x3); ptile3 takes the bias at run time in every set
+constexpr XmcEpiList<kEpiRes, kEpiBias, 0> kEpiClasses{};
+constexpr XmcEpiList<kEpiRes, 0> kEpiClassesPtile{};
+// 3x3: plain / bias only (the data gradients, the forwards without a block end; wtile2: the attention-modulation blocks' convolutions) ...
+constexpr XmcEpiList<0, kEpiBias, kEpiBias | kEpiLrelu> kEpiPlain{};
+// ... and on ptile3's 16x16x32 role the generator's last block: c2 + block sum + the tail's LeakyReLU
+constexpr XmcEpiList<0, (kEpiGSum | kEpiPost) & ~kEpiBias> kEpiPlainPtile{};
+// Calls go(std::integral_constant<int, E>) for the E of the list that equals `mask` and hands its result to *rc; false when the list
+// has no such entry (nothing was called).
+template <int... E, typename F>
+static inline bool xmc_epi_launch(XmcEpiList<E...>, int mask, int* rc, F&& go) {
+    return ((mask == E && ((*rc = go(std::integral_constant<int, E>{})), true)) || ...);
 }
 
 // residual index (in 8-channel units) of destination pixel (n, y, x) for the three residual layouts; (a, b) is the pixel's

@@ -363,14 +363,10 @@ int launch_splitk(const XmcConvDesc& d, int S, hipStream_t st) {
     const int64_t M = (int64_t)d.N * d.MH * d.MW;
     dim3 grid((unsigned)(((M + BM - 1) / BM) * (d.CDw / BN)), (unsigned)S, (unsigned)d.nclass);
     using Lds = IgemmLds<BM, BN, 2>;
-    size_t dyn = 0;
-    if (Lds::DYNAMIC) {
-        dyn = (size_t)Lds::SMEM_U * 16;
-        XMC_ALLOW_BIG_LDS((igemm_kernel<XMC_BF16, BM, BN, WM, WN, 2, true>));
-    }
-    hipLaunchKernelGGL((igemm_kernel<XMC_BF16, BM, BN, WM, WN, 2, true>), grid, dim3(64 * WM * WN), dyn, st, d);
-    xmc_note_kernel("igemm_kernel<%d, %d, %d, %d, %d, %d, true>", XMC_BF16, BM, BN, WM, WN, 2);     // (SK = true: the name rocprof prints)
-    XMC_LAUNCH_CHECK();
+    const size_t dyn = Lds::DYNAMIC ? (size_t)Lds::SMEM_U * 16 : 0;
+    const int rc = xmc_launch<&igemm_kernel<XMC_BF16, BM, BN, WM, WN, 2, true>, Lds::DYNAMIC>(
+        grid, dim3(64 * WM * WN), dyn, st, {"igemm_kernel<%d, %d, %d, %d, %d, %d, true>", {XMC_BF16, BM, BN, WM, WN, 2}}, d);     // (SK = true: the name rocprof prints)
+    if (rc != 0) return rc;
     const int64_t items = M * (d.CD / 8);
     hipLaunchKernelGGL(igemm_splitk_finish_kernel, dim3((unsigned)((items + 256 * SK_FIN_ITEMS - 1) / (256 * SK_FIN_ITEMS)), 1, (unsigned)d.nclass), dim3(256), 0, st, d, S);
     XMC_LAUNCH_CHECK();
@@ -382,15 +378,9 @@ int launch(const XmcConvDesc& d, hipStream_t st) {
     const int64_t M = (int64_t)d.N * d.MH * d.MW;
     dim3 grid((unsigned)(((M + BM - 1) / BM) * (d.CDw / BN)), 1, (unsigned)d.nclass);
     using Lds = IgemmLds<BM, BN, KSUB>;
-    size_t dyn = 0;
-    if (Lds::DYNAMIC) {
-        dyn = (size_t)Lds::SMEM_U * 16;
-        XMC_ALLOW_BIG_LDS((igemm_kernel<DT, BM, BN, WM, WN, KSUB>));
-    }
-    hipLaunchKernelGGL((igemm_kernel<DT, BM, BN, WM, WN, KSUB>), grid, dim3(64 * WM * WN), dyn, st, d);
-    xmc_note_kernel("igemm_kernel<%d, %d, %d, %d, %d, %d>", DT, BM, BN, WM, WN, KSUB);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    const size_t dyn = Lds::DYNAMIC ? (size_t)Lds::SMEM_U * 16 : 0;
+    return xmc_launch<&igemm_kernel<DT, BM, BN, WM, WN, KSUB>, Lds::DYNAMIC>(grid, dim3(64 * WM * WN), dyn, st,
+                                                                           {"igemm_kernel<%d, %d, %d, %d, %d, %d>", {DT, BM, BN, WM, WN, KSUB}}, d);
 }
 
 template <int DT>

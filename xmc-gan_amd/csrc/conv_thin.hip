@@ -11,6 +11,7 @@
 //     BN/4 consecutive output channels of one pixel and stores 16-byte units straight from registers.
 // HBM traffic = source once (+6 % halo) + destination once.
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -1111,18 +1112,14 @@ int xmc_conv_thin_out_try(const XmcConvDesc* d, void* stream) {
     if (d->SA != 1 || d->DA != 1 || d->src_shift != 0 || d->nclass != 1 || d->ntaps != 9 || d->groups > 1) return 1;
     if (d->res || d->mask || d->alpha_dev || d->dst2 || d->dst_pool || d->post_act || d->sign_bits || d->dot) return 1;
     if (d->act != XMC_ACT_NONE && d->act != XMC_ACT_TANH && d->act != XMC_ACT_LRELU) return 1;
-    if (d->MH % TO_H != 0 || d->MW % TO_W != 0 || d->SH != d->MH || d->SW != d->MW || d->DH != d->MH || d->DW != d->MW) return 1;
-    if (d->dph[0] != 0 || d->dpw[0] != 0) return 1;
-    for (int k = 0; k < 9; ++k)
-        if (d->dh[0][k] < -1 || d->dh[0][k] > 1 || d->dw[0][k] < -1 || d->dw[0][k] > 1) return 1;
+    if (d->MH % TO_H != 0 || d->MW % TO_W != 0 || !xmc_same_size_maps(d)) return 1;
+    if (d->dph[0] != 0 || d->dpw[0] != 0 || !xmc_taps_within(d, 0, 1)) return 1;
     const int tx = d->MW / TO_W, ty = d->MH / TO_H, ntiles = d->N * tx * ty;
     const int grid = ntiles < 256 * 8 ? ntiles : 256 * 8;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->CS == 32) hipLaunchKernelGGL((thin_out_kernel<1>), dim3(xmc_ab_grid(grid)), dim3(256), 0, st, *d, tx, ty, ntiles);
-    else hipLaunchKernelGGL((thin_out_kernel<2>), dim3(xmc_ab_grid(grid)), dim3(256), 0, st, *d, tx, ty, ntiles);
-    xmc_note_kernel("thin_out_kernel<%d>", d->CS / 32);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    const XmcKName name = {"thin_out_kernel<%d>", {d->CS / 32}};
+    if (d->CS == 32) return xmc_launch<&thin_out_kernel<1>, false>(dim3(xmc_ab_grid(grid)), dim3(256), 0, st, name, *d, tx, ty, ntiles);
+    return xmc_launch<&thin_out_kernel<2>, false>(dim3(xmc_ab_grid(grid)), dim3(256), 0, st, name, *d, tx, ty, ntiles);
 }
 
 // 0 = launched, 1 = not this kernel's case, < 0 = error
@@ -1133,32 +1130,22 @@ int xmc_conv_thin_try(const XmcConvDesc* d, void* stream) {
     if (d->SA != 1 || d->DA != 1 || d->src_shift != 0 || d->nclass != 1 || d->ntaps > 12) return 1;
     if (d->CDw != 32 && d->CDw != 64) return 1;
     if (d->res || d->alpha_dev || d->dst2 || d->post_act || d->sign_bits || d->dot || (d->act != XMC_ACT_NONE && d->act != XMC_ACT_LRELU)) return 1;
-    if (d->MH % 8 != 0 || d->MW % 32 != 0 || d->SH != d->MH || d->SW != d->MW || d->DH != d->MH || d->DW != d->MW) return 1;
+    if (d->MH % 8 != 0 || d->MW % 32 != 0 || !xmc_same_size_maps(d)) return 1;
     if (d->dph[0] != 0 || d->dpw[0] != 0) return 1;
-    int hmin = 127, hmax = -128, wmin = 127, wmax = -128;
-    for (int k = 0; k < d->ntaps; ++k) {
-        const int h = d->dh[0][k], w = d->dw[0][k];
-        hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-        wmin = w < wmin ? w : wmin; wmax = w > wmax ? w : wmax;
-    }
-    if (hmax - hmin > 4 || wmax - wmin > 4 || hmin > 0 || wmin > 0 || hmax < 0 || wmax < 0) return 1;
+    const XmcTapBox b = xmc_tap_box(d, 0);
+    if (b.hmax - b.hmin > 4 || b.wmax - b.wmin > 4 || b.hmin > 0 || b.wmin > 0 || b.hmax < 0 || b.wmax < 0) return 1;
     ThinCfg t;
     t.tiles_y = d->MH / 8; t.tiles_x = d->MW / 32;
-    t.PH = 8 + (hmax - hmin); t.PW = 32 + (wmax - wmin);
-    t.dh0 = hmin; t.dw0 = wmin;
+    t.PH = 8 + (b.hmax - b.hmin); t.PW = 32 + (b.wmax - b.wmin);
+    t.dh0 = b.hmin; t.dw0 = b.wmin;
     if (t.PH * t.PW > 512) return 1;
     const int ntiles = d->N * t.tiles_y * t.tiles_x;
     int gx = 256 * 5;
     if (gx > ntiles) gx = ntiles;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->CDw == 32) {
-        hipLaunchKernelGGL((thin_in_kernel<32>), dim3(xmc_ab_grid(gx)), dim3(256), 0, st, *d, t, ntiles);
-    } else {
-        hipLaunchKernelGGL((thin_in_kernel<64>), dim3(xmc_ab_grid(gx)), dim3(256), 0, st, *d, t, ntiles);
-    }
-    xmc_note_kernel("thin_in_kernel<%d>", d->CDw);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    const XmcKName name = {"thin_in_kernel<%d>", {d->CDw}};
+    if (d->CDw == 32) return xmc_launch<&thin_in_kernel<32>, false>(dim3(xmc_ab_grid(gx)), dim3(256), 0, st, name, *d, t, ntiles);
+    return xmc_launch<&thin_in_kernel<64>, false>(dim3(xmc_ab_grid(gx)), dim3(256), 0, st, name, *d, t, ntiles);
 }
 
 // The generator tail's backward in one pass (gtail_bwd_kernel; include/xmc_gan_hip.h).  0 = launched, 1 = not this kernel's case, < 0 = error
@@ -1172,7 +1159,7 @@ extern "C" int xmc_gtail_bwd(const XmcConvDesc* d, const void* img, float* dwp, 
     if (d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16 || d->CS != 8 || d->CD != 32 || d->CDw != 32) return 1;
     if (d->SA != 1 || d->DA != 1 || d->src_shift != 0 || d->nclass != 1 || d->ntaps != 9 || d->groups > 1) return 1;
     if (d->bias || d->res || d->alpha_dev || d->dst2 || d->post_act || d->sign_bits || d->dot || d->act != XMC_ACT_NONE) return 1;
-    if (d->MH % 8 != 0 || d->MW % 2 != 0 || d->SH != d->MH || d->SW != d->MW || d->DH != d->MH || d->DW != d->MW) return 1;
+    if (d->MH % 8 != 0 || d->MW % 2 != 0 || !xmc_same_size_maps(d)) return 1;
     if (d->dph[0] != 0 || d->dpw[0] != 0) return 1;
     for (int t = 0; t < 9; ++t)         // the 3x3, pad-1 data gradient in its natural tap order: tap t reads dpre at (+1 - t / 3, +1 - t % 3)
         if (d->dh[0][t] != 1 - t / 3 || d->dw[0][t] != 1 - t % 3 || d->wi[0][t] != t) return 1;
@@ -1247,7 +1234,7 @@ static int pw1x1_go(const XmcConvDesc* d, void* stream, const unsigned char* sbi
     if (d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16) return 1;
     if (d->ntaps != 1 || d->nclass != 1 || d->SA != 1 || d->DA != 1 || d->src_shift != 0) return 1;
     if (d->dh[0][0] != 0 || d->dw[0][0] != 0 || d->dph[0] != 0 || d->dpw[0] != 0) return 1;
-    if (d->SH != d->MH || d->SW != d->MW || d->DH != d->MH || d->DW != d->MW) return 1;
+    if (!xmc_same_size_maps(d)) return 1;
     if (d->post_act || d->sign_bits || d->dot) return 1;
     if (d->res || d->mask || d->alpha_dev || d->dst2 || (d->act != XMC_ACT_NONE && d->act != XMC_ACT_LRELU)) return 1;
     if (d->CS % 32 != 0 || d->CDw % 32 != 0 || d->CD % 8 != 0) return 1;

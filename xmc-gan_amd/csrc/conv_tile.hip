@@ -17,6 +17,7 @@
 // caller ever used it: the weight gradient of the same layer needs the activated tensor as its operand, so the tensor has to
 // exist in HBM anyway and the fusion only moved a pass from the forward to the backward.  Removed in round 2.)
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -984,37 +985,41 @@ __global__ __launch_bounds__(512) void ptile3_kernel(const XmcConvDesc d, const 
     }
 }
 
+// XMC_DEBUG_DISPATCH=no_ptile_epi: every launch of the persistent kernel through its descriptor-reading epilogue
+bool no_ptile_epi() {
+    static const bool off = xmc_debug_off("no_ptile_epi");
+    return off;
+}
+// persistent, weights resident: a slice's source channels are one slab and its rows one or two 32-channel blocks
+bool ptile_resident(const XmcConvDesc& d, const TileCfg& t) { return d.CS <= 64 && t.slab == d.CS && d.CDw <= 64; }
+
 template <int BN>
 int launch_ptile(const XmcConvDesc& d, const TileCfg& t, hipStream_t st) {
     // (a descriptor with sc_img is served by the 32x32x16 block-end sets below or not at all)
     if (d.sc_img && !(d.SA == 1 && d.ntaps == 9 && d.nclass == 1 && t.slab == 64 && d.out_dtype == XMC_BF16 && (d.dst_pool || d.sign_bits))) return XMC_ESHAPE;
     int maxpatch = 0;
     for (int z = 0; z < d.nclass; ++z) maxpatch = t.PH[z] * t.PW[z] > maxpatch ? t.PH[z] * t.PW[z] : maxpatch;
+    // The epilogue option sets of the training step as compile-time instantiations (common.h: the kEpi* lists), anything else through
+    // the descriptor-reading one.  Every role but the 32x32x16 one takes the bias at run time in all of its sets.
+    const int epi = no_ptile_epi() ? -1 : xmc_epi_mask(d);
+    const int epi_nb = no_ptile_epi() ? -1 : (epi & ~kEpiBias);           // (< 0 stays < 0: bit 0 of -1 cleared is -2)
+    const dim3 block(512);
+    int rc;
     if (d.SA == 2) {                                                  // 4x4 stride 2, 32 input channels: 612-pixel patch in planes
         const size_t lds2 = (size_t)((maxpatch * 96 + 15) & ~15) + (size_t)16 * BN * 96;
         if (lds2 > XMC_MAX_DYN_LDS || t.slab != 32) return XMC_ESHAPE;
         const int nt2 = d.N * t.tiles_y * t.tiles_x;
         int g2 = 256 / (int)(d.CDw / BN);
         if (g2 > nt2) g2 = nt2;
-        static const bool no_epi2 = xmc_debug_off("no_ptile_epi");
-        const int epi2 = no_epi2 ? -1 : (xmc_epi_mask(d) & ~kEpiBias);          // (< 0 stays < 0: bit 0 of -1 cleared is -2)
-#define XMC_PT3S2(E)                                                                                                        \
-        if (epi2 == (E)) {                                                                                                  \
-            XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 32, 16, 1, 2, false, (E)>));                                               \
-            hipLaunchKernelGGL((ptile3_kernel<BN, 32, 16, 1, 2, false, (E)>), dim3(g2, d.CDw / BN, 1), dim3(512), lds2, st, d, t, nt2); \
-            xmc_note_kernel("ptile3_kernel<%d, 32, 16, 1, 2>", BN);                                                         \
-            XMC_LAUNCH_CHECK();                                                                                             \
-            return 0;                                                                                                       \
-        }
-        XMC_PT3S2(kEpiLrelu) XMC_PT3S2(0) XMC_PT3S2(kEpiMask)
-#undef XMC_PT3S2
+        const dim3 grid2(g2, d.CDw / BN, 1);
+        const XmcKName name = {"ptile3_kernel<%d, 32, 16, 1, 2>", {BN}};
+        if (xmc_epi_launch(kEpiStride2, epi_nb, &rc, [&](auto e) {
+                return xmc_launch<&ptile3_kernel<BN, 32, 16, 1, 2, false, decltype(e)::value>>(grid2, block, lds2, st, name, d, t, nt2);
+            }))
+            return rc;
         if (d.sign_bits || d.dot) return XMC_ESHAPE;     // only compile-time option sets carry these two
-        xmc_note_generic_epi("ptile3<s2>", epi2);
-        XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 32, 16, 1, 2>));
-        hipLaunchKernelGGL((ptile3_kernel<BN, 32, 16, 1, 2>), dim3(g2, d.CDw / BN, 1), dim3(512), lds2, st, d, t, nt2);
-        xmc_note_kernel("ptile3_kernel<%d, 32, 16, 1, 2>", BN);
-        XMC_LAUNCH_CHECK();
-        return 0;
+        xmc_note_generic_epi("ptile3<s2>", epi_nb);
+        return xmc_launch<&ptile3_kernel<BN, 32, 16, 1, 2>>(grid2, block, lds2, st, name, d, t, nt2);
     }
     if (maxpatch > 384) return XMC_ESHAPE;                            // staging registers: PIT * 256 / cps pixels
     const int pstride = t.slab * 2 + 32;
@@ -1026,25 +1031,16 @@ int launch_ptile(const XmcConvDesc& d, const TileCfg& t, hipStream_t st) {
     int gx = 256 * per_cu / (int)((d.CDw / BN) * d.nclass);
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
-    dim3 grid((unsigned)gx, (unsigned)(d.CDw / BN), (unsigned)d.nclass);
+    const dim3 grid((unsigned)gx, (unsigned)(d.CDw / BN), (unsigned)d.nclass);
     if (t.slab == 128) {                                                // one class per blockIdx.z, its four 128-deep slices resident
         if (BN != 64 || d.ntaps != 4 || d.sign_bits || d.dot) return XMC_ESHAPE;
-        const int epis = xmc_debug_off("no_ptile_epi") ? -1 : (xmc_epi_mask(d) & ~kEpiBias);
-#define XMC_PT3W(E)                                                                                                         \
-        if (epis == (E)) {                                                                                                  \
-            XMC_ALLOW_BIG_LDS((ptile3_kernel<64, 128, 4, 1, 1, false, (E)>));                                               \
-            hipLaunchKernelGGL((ptile3_kernel<64, 128, 4, 1, 1, false, (E)>), grid, dim3(512), lds, st, d, t, ntiles);      \
-        } else
-        XMC_PT3W(kEpiRes) XMC_PT3W(0)
-#undef XMC_PT3W
-        {
-            xmc_note_generic_epi("ptile3<128>", epis);
-            XMC_ALLOW_BIG_LDS((ptile3_kernel<64, 128, 4, 1>));
-            hipLaunchKernelGGL((ptile3_kernel<64, 128, 4, 1>), grid, dim3(512), lds, st, d, t, ntiles);
-        }
-        xmc_note_kernel("ptile3_kernel<64, 128, 4, 1>");
-        XMC_LAUNCH_CHECK();
-        return 0;
+        const XmcKName name = {"ptile3_kernel<64, 128, 4, 1>", {}};
+        if (xmc_epi_launch(kEpiClassesPtile, epi_nb, &rc, [&](auto e) {
+                return xmc_launch<&ptile3_kernel<64, 128, 4, 1, 1, false, decltype(e)::value>>(grid, block, lds, st, name, d, t, ntiles);
+            }))
+            return rc;
+        xmc_note_generic_epi("ptile3<128>", epi_nb);
+        return xmc_launch<&ptile3_kernel<64, 128, 4, 1>>(grid, block, lds, st, name, d, t, ntiles);
     }
     // all 4 output-parity classes from one staged patch when their 16 weight slices fit beside it
     if (d.nclass == 4 && d.ntaps == 4 && t.PHu * t.PWu <= 384) {
@@ -1053,102 +1049,58 @@ int launch_ptile(const XmcConvDesc& d, const TileCfg& t, hipStream_t st) {
         if (ldsm <= XMC_MAX_DYN_LDS && !no_merge) {
             int gm = 256 / (int)(d.CDw / BN);
             if (gm > ntiles) gm = ntiles;
-            dim3 gridm((unsigned)gm, (unsigned)(d.CDw / BN), 1);
+            const dim3 gridm((unsigned)gm, (unsigned)(d.CDw / BN), 1);
             if (d.sign_bits || d.dot) return XMC_ESHAPE;
-            static const bool no_epim = xmc_debug_off("no_ptile_epi");
-            const int epim = no_epim ? -1 : (xmc_epi_mask(d) & ~kEpiBias);
-#define XMC_PT3M(SL, E)                                                                                                     \
-            if (t.slab == (SL) && epim == (E)) {                                                                            \
-                XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, SL, 4, 4, 1, false, (E)>));                                            \
-                hipLaunchKernelGGL((ptile3_kernel<BN, SL, 4, 4, 1, false, (E)>), gridm, dim3(512), ldsm, st, d, t, ntiles); \
-            } else
-            XMC_PT3M(64, kEpiRes) XMC_PT3M(64, 0) XMC_PT3M(32, kEpiRes) XMC_PT3M(32, 0)
-#undef XMC_PT3M
-            if (t.slab == 64) {
-                xmc_note_generic_epi("ptile3<4,4>", epim);
-                XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 64, 4, 4>));
-                hipLaunchKernelGGL((ptile3_kernel<BN, 64, 4, 4>), gridm, dim3(512), ldsm, st, d, t, ntiles);
-            } else {
-                XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 32, 4, 4>));
-                hipLaunchKernelGGL((ptile3_kernel<BN, 32, 4, 4>), gridm, dim3(512), ldsm, st, d, t, ntiles);
-            }
-            xmc_note_kernel("ptile3_kernel<%d, %d, 4, 4>", BN, t.slab);
-            XMC_LAUNCH_CHECK();
-            return 0;
+            const XmcKName name = {"ptile3_kernel<%d, %d, 4, 4>", {BN, t.slab}};
+            auto merged = [&](auto sl) -> int {
+                constexpr int SL = decltype(sl)::value;
+                if (xmc_epi_launch(kEpiClassesPtile, epi_nb, &rc, [&](auto e) {
+                        return xmc_launch<&ptile3_kernel<BN, SL, 4, 4, 1, false, decltype(e)::value>>(gridm, block, ldsm, st, name, d, t, ntiles);
+                    }))
+                    return rc;
+                if (SL == 64) xmc_note_generic_epi("ptile3<4,4>", epi_nb);
+                return xmc_launch<&ptile3_kernel<BN, SL, 4, 4>>(gridm, block, ldsm, st, name, d, t, ntiles);
+            };
+            return t.slab == 64 ? merged(std::integral_constant<int, 64>{}) : merged(std::integral_constant<int, 32>{});
         }
     }
     static const bool no_m32 = xmc_debug_off("no_ptile_m32");
     if (!no_m32 && d.ntaps == 9 && d.out_dtype == XMC_BF16 && t.slab == 64 &&
         (d.res || d.dst2 || d.dst_pool || d.mask || d.sign_bits)) {      // one matrix wave per SIMD: 32x32x16 form
-        // the epilogue option sets of the training step as compile-time instantiations (kEpi*), anything else through the
-        // descriptor-reading one
-        int epi = xmc_epi_mask(d);
-        static const bool no_epi = xmc_debug_off("no_ptile_epi");
-        if (no_epi) epi = -1;
         if (d.sc_img) {                           // the residual recomputed from the image (xmc_conv_ptile_scimg): two block-end sets, 8 x 32 tiles
             if (BN != 64 || d.res || t.TW != 32 || d.CD != 64 || lds + 18 * 66 * 8 > XMC_MAX_DYN_LDS) return XMC_ESHAPE;
-#define XMC_PT3_SCI(E)                                                                                                   \
-            if (epi == (E)) {                                                                                            \
-                XMC_ALLOW_BIG_LDS((ptile3_kernel<64, 64, 9, 1, 1, true, (E)>));                                          \
-                hipLaunchKernelGGL((ptile3_kernel<64, 64, 9, 1, 1, true, (E)>), grid, dim3(512), lds + 18 * 66 * 8, st, d, t, ntiles); \
-                xmc_note_kernel("ptile3_kernel<64, 64, 9, 1, 1, true, sc>");                                             \
-                XMC_LAUNCH_CHECK();                                                                                      \
-                return 0;                                                                                                \
-            }
-            XMC_PT3_SCI((kEpiDKeepS & ~kEpiRes) | kEpiScImg) XMC_PT3_SCI((kEpiDFwd & ~kEpiRes) | kEpiScImg)
-#undef XMC_PT3_SCI
+            const XmcKName name = {"ptile3_kernel<64, 64, 9, 1, 1, true, sc>", {}};
+            if (xmc_epi_launch(kEpiBlockEndScImg, epi, &rc, [&](auto e) {
+                    return xmc_launch<&ptile3_kernel<64, 64, 9, 1, 1, true, decltype(e)::value>>(grid, block, lds + 18 * 66 * 8, st, name, d, t, ntiles);
+                }))
+                return rc;
             return XMC_ESHAPE;
         }
-#define XMC_PT3_EPI(E)                                                                                                   \
-        if (epi == (E)) {                                                                                                \
-            XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 64, 9, 1, 1, true, (E)>));                                              \
-            hipLaunchKernelGGL((ptile3_kernel<BN, 64, 9, 1, 1, true, (E)>), grid, dim3(512), lds, st, d, t, ntiles);     \
-            xmc_note_kernel("ptile3_kernel<%d, 64, 9, 1, 1, true>", BN);                                                 \
-            XMC_LAUNCH_CHECK();                                                                                          \
-            return 0;                                                                                                    \
-        }
-        XMC_PT3_EPI(kEpiGSum) XMC_PT3_EPI(kEpiDKeep) XMC_PT3_EPI(kEpiDFwd) XMC_PT3_EPI(kEpiDLast) XMC_PT3_EPI(kEpiDLin)
-        XMC_PT3_EPI(kEpiDKeepS) XMC_PT3_EPI(kEpiDLastS) XMC_PT3_EPI(kEpiDgDot)
-        XMC_PT3_EPI(kEpiMask)                                                                // data gradient through a LeakyReLU
-#undef XMC_PT3_EPI
+        const XmcKName name = {"ptile3_kernel<%d, 64, 9, 1, 1, true>", {BN}};
+        if (xmc_epi_launch(kEpiBlockEnd, epi, &rc, [&](auto e) {
+                return xmc_launch<&ptile3_kernel<BN, 64, 9, 1, 1, true, decltype(e)::value>>(grid, block, lds, st, name, d, t, ntiles);
+            }))
+            return rc;
         if (d.sign_bits || d.dot) return XMC_ESHAPE;
         xmc_note_generic_epi("ptile3<M32>", epi);
-        XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, 64, 9, 1, 1, true>));
-        hipLaunchKernelGGL((ptile3_kernel<BN, 64, 9, 1, 1, true>), grid, dim3(512), lds, st, d, t, ntiles);
-        xmc_note_kernel("ptile3_kernel<%d, 64, 9, 1, 1, true>", BN);
-        XMC_LAUNCH_CHECK();
-        return 0;
+        return xmc_launch<&ptile3_kernel<BN, 64, 9, 1, 1, true>>(grid, block, lds, st, name, d, t, ntiles);
     }
-#define XMC_PT3(SL, NTP)                                                                                                      \
-    do {                                                                                                                      \
-        XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, SL, NTP, 1>));                                                                   \
-        hipLaunchKernelGGL((ptile3_kernel<BN, SL, NTP, 1>), grid, dim3(512), lds, st, d, t, ntiles);                          \
-        xmc_note_kernel("ptile3_kernel<%d, %d, %d, 1>", BN, SL, NTP);                                                         \
-    } while (0)
-    static const bool no_epi9 = xmc_debug_off("no_ptile_epi");
-    const int epi9 = (no_epi9 || d.ntaps != 9) ? -1 : (xmc_epi_mask(d) & ~kEpiBias);
-#define XMC_PT3E(SL, E)                                                                                                       \
-    if (t.slab == (SL) && epi9 == (E)) {                                                                                      \
-        XMC_ALLOW_BIG_LDS((ptile3_kernel<BN, SL, 9, 1, 1, false, (E)>));                                                      \
-        hipLaunchKernelGGL((ptile3_kernel<BN, SL, 9, 1, 1, false, (E)>), grid, dim3(512), lds, st, d, t, ntiles);             \
-        xmc_note_kernel("ptile3_kernel<%d, %d, %d, 1>", BN, SL, 9);                                                           \
-        XMC_LAUNCH_CHECK();                                                                                                   \
-        return 0;                                                                                                             \
-    }
-    // plain / bias only (the data gradients, the 64 -> 64 forward without a block end) and the generator's last block: c2 + block sum
-    // + the tail's LeakyReLU
-    XMC_PT3E(64, 0) XMC_PT3E(32, 0) XMC_PT3E(32, (kEpiGSum | kEpiPost) & ~kEpiBias) XMC_PT3E(64, (kEpiGSum | kEpiPost) & ~kEpiBias)
-#undef XMC_PT3E
-    if (d.sign_bits || d.dot) return XMC_ESHAPE;
-    xmc_note_generic_epi("ptile3<16x16>", epi9);
-    if (t.slab == 64) {
-        if (d.ntaps == 9) XMC_PT3(64, 9); else if (d.ntaps == 4) XMC_PT3(64, 4); else XMC_PT3(64, 0);
-    } else {
-        if (d.ntaps == 9) XMC_PT3(32, 9); else if (d.ntaps == 4) XMC_PT3(32, 4); else XMC_PT3(32, 0);
-    }
-#undef XMC_PT3
-    XMC_LAUNCH_CHECK();
-    return 0;
+    // 16x16x32 form.  3x3: plain / bias only and the generator's last block (kEpiPlainPtile)
+    const int epi9 = d.ntaps != 9 ? -1 : epi_nb;
+    auto plain = [&](auto sl) -> int {
+        constexpr int SL = decltype(sl)::value;
+        const XmcKName name = {"ptile3_kernel<%d, %d, %d, 1>", {BN, SL, d.ntaps == 9 ? 9 : d.ntaps == 4 ? 4 : 0}};
+        if (xmc_epi_launch(kEpiPlainPtile, epi9, &rc, [&](auto e) {
+                return xmc_launch<&ptile3_kernel<BN, SL, 9, 1, 1, false, decltype(e)::value>>(grid, block, lds, st, name, d, t, ntiles);
+            }))
+            return rc;
+        if (d.sign_bits || d.dot) return XMC_ESHAPE;
+        xmc_note_generic_epi("ptile3<16x16>", epi9);
+        if (d.ntaps == 9) return xmc_launch<&ptile3_kernel<BN, SL, 9, 1>>(grid, block, lds, st, name, d, t, ntiles);
+        if (d.ntaps == 4) return xmc_launch<&ptile3_kernel<BN, SL, 4, 1>>(grid, block, lds, st, name, d, t, ntiles);
+        return xmc_launch<&ptile3_kernel<BN, SL, 0, 1>>(grid, block, lds, st, name, d, t, ntiles);
+    };
+    return t.slab == 64 ? plain(std::integral_constant<int, 64>{}) : plain(std::integral_constant<int, 32>{});
 }
 
 template <int BN, int WM, int WN>
@@ -1160,12 +1112,8 @@ int launch_tile(const XmcConvDesc& d, const TileCfg& t, hipStream_t st) {
     size_t ep = (size_t)128 * (BN + 4) * 4;
     if (ep > lds) lds = ep;
     if (lds > XMC_MAX_DYN_LDS) return XMC_ESHAPE;
-    XMC_ALLOW_BIG_LDS((tile_kernel<BN, WM, WN>));
-    dim3 grid((unsigned)(d.N * t.tiles_y * t.tiles_x), (unsigned)(d.CDw / BN), (unsigned)d.nclass);
-    hipLaunchKernelGGL((tile_kernel<BN, WM, WN>), grid, dim3(256), lds, st, d, t);
-    xmc_note_kernel("tile_kernel<%d, %d, %d>", BN, WM, WN);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid((unsigned)(d.N * t.tiles_y * t.tiles_x), (unsigned)(d.CDw / BN), (unsigned)d.nclass);
+    return xmc_launch<&tile_kernel<BN, WM, WN>>(grid, dim3(256), lds, st, {"tile_kernel<%d, %d, %d>", {BN, WM, WN}}, d, t);
 }
 
 }  // namespace
@@ -1193,14 +1141,9 @@ static int tile_plan(const XmcConvDesc* d, TileCfg* t) {
     static const bool no_s128 = xmc_debug_off("no_ptile_slab128");
     if (!no_s128 && d->CS == 128 && d->SA == 1 && d->ntaps == 4 && d->nclass == 4 && d->CDw == 64 && d->out_dtype == XMC_BF16) t->slab = 128;
     for (int z = 0; z < d->nclass; ++z) {
-        int hmin = 127, hmax = -128, wmin = 127, wmax = -128;
-        for (int k = 0; k < d->ntaps; ++k) {
-            int h = d->dh[z][k], w = d->dw[z][k];
-            hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-            wmin = w < wmin ? w : wmin; wmax = w > wmax ? w : wmax;
-        }
-        t->dh0[z] = hmin; t->dw0[z] = wmin;
-        t->PH[z] = d->SA * (TH - 1) + (hmax - hmin + 1); t->PW[z] = d->SA * (TW - 1) + (wmax - wmin + 1);
+        const XmcTapBox b = xmc_tap_box(d, z);
+        t->dh0[z] = b.hmin; t->dw0[z] = b.wmin;
+        t->PH[z] = d->SA * (TH - 1) + (b.hmax - b.hmin + 1); t->PW[z] = d->SA * (TW - 1) + (b.wmax - b.wmin + 1);
         if (s2 ? (t->PH[z] > 18 || t->PW[z] > 34 || (t->PW[z] & 1)) : (t->PH[z] * t->PW[z] > (t->slab == 128 ? 384 : 12 * (256 / (t->slab / 8))))) return 0;   // staging registers (PIT)
     }
     {
@@ -1220,7 +1163,7 @@ int xmc_conv_ptile_pool_try(const XmcConvDesc* d, void* stream) {
     TileCfg t;
     if (!d->dst_pool || d->out_dtype != XMC_BF16 || d->SA != 1 || d->DA != 1 || d->nclass != 1 || (d->DH & 1) || (d->DW & 1)) return 1;
     if (!tile_plan(d, &t)) return 1;
-    if (!(d->CS <= 64 && t.slab == d->CS && d->CDw <= 64) || xmc_debug_off("no_ptile")) return 1;
+    if (!ptile_resident(*d, t) || xmc_debug_off("no_ptile")) return 1;
     const int rc = d->CDw == 64 ? launch_ptile<64>(*d, t, reinterpret_cast<hipStream_t>(stream))
                                 : launch_ptile<32>(*d, t, reinterpret_cast<hipStream_t>(stream));
     return rc == XMC_ESHAPE ? 1 : rc;
@@ -1231,11 +1174,9 @@ extern "C" int xmc_conv_ptile_scimg(const XmcConvDesc* d, void* stream) {
     if (!d || !d->src || !d->wpk || !d->dst || !d->sc_img || !d->sc_frag || !d->sc_bias) return XMC_EINVAL;
     static const bool off = xmc_debug_off("no_scimg");
     if (off || d->res || d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16 || d->SA != 1 || d->DA != 1 || d->nclass != 1 || d->ntaps != 9 ||
-        d->src_shift != 0 || d->CS != 64 || d->CDw != 64 || d->CD != 64 || d->MW % 32 != 0 || d->MH % 8 != 0 || d->SH != d->MH || d->SW != d->MW ||
-        d->DH != d->MH || d->DW != d->MW || xmc_debug_off("no_ptile") || xmc_debug_off("no_ptile_m32") || xmc_debug_off("no_ptile_epi"))
+        d->src_shift != 0 || d->CS != 64 || d->CDw != 64 || d->CD != 64 || d->MW % 32 != 0 || d->MH % 8 != 0 || !xmc_same_size_maps(d) ||
+        xmc_debug_off("no_ptile") || xmc_debug_off("no_ptile_m32") || no_ptile_epi() || !xmc_taps_within(d, 0, 1))
         return 1;
-    for (int k = 0; k < 9; ++k)
-        if (d->dh[0][k] < -1 || d->dh[0][k] > 1 || d->dw[0][k] < -1 || d->dw[0][k] > 1) return 1;
     TileCfg t;
     if (!tile_plan(d, &t) || t.slab != 64) return 1;
     const int rc = launch_ptile<64>(*d, t, reinterpret_cast<hipStream_t>(stream));
@@ -1249,7 +1190,7 @@ extern "C" int xmc_conv_ptile_bits(const XmcConvDesc* d, void* stream) {
     if (off || d->dtype != XMC_BF16 || d->SA != 1 || d->DA != 1 || d->nclass != 1 || d->src_shift != 0 || d->dst_pool) return 1;
     TileCfg t;
     if (!tile_plan(d, &t)) return 1;
-    if (!(d->CS <= 64 && t.slab == d->CS && d->CDw <= 64) || xmc_debug_off("no_ptile")) return 1;
+    if (!ptile_resident(*d, t) || xmc_debug_off("no_ptile")) return 1;
     const int rc = d->CDw == 64 ? launch_ptile<64>(*d, t, reinterpret_cast<hipStream_t>(stream))
                                 : launch_ptile<32>(*d, t, reinterpret_cast<hipStream_t>(stream));
     return rc == XMC_ESHAPE ? 1 : rc;
@@ -1272,7 +1213,7 @@ int xmc_conv_tile_try(const XmcConvDesc* d, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
     static const bool no_pt = xmc_debug_off("no_ptile");
-    if (!no_pt && d->CS <= 64 && t.slab == d->CS && d->CDw <= 64) {          // persistent, weights resident
+    if (!no_pt && ptile_resident(*d, t)) {
         rc = d->CDw == 64 ? launch_ptile<64>(*d, t, st) : launch_ptile<32>(*d, t, st);
         if (rc != XMC_ESHAPE) return rc;
     }

@@ -8,6 +8,7 @@
 // the very end.  HBM traffic = each activation read ~1.3x, once.
 // MFMA operands are pixel-major in LDS, fragments come from ds_read_b64_tr_b16 (see conv_wgrad.hip).
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -626,14 +627,9 @@ static int wgrad_tile_go(const XmcConvDesc* d, float* dwp, float* dbias, void* s
     if (d->CD % 8 != 0 || d->CS % 8 != 0) return 1;
     WTCfg t;
     t.tiles_y = d->MH / TH; t.tiles_x = d->MW / TW; t.ntiles = d->N * t.tiles_y * t.tiles_x;
-    int hmin = 127, hmax = -128, wmin = 127, wmax = -128;
-    for (int k = 0; k < d->ntaps; ++k) {
-        int h = d->dh[0][k], w = d->dw[0][k];
-        hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-        wmin = w < wmin ? w : wmin; wmax = w > wmax ? w : wmax;
-    }
-    t.dh0 = hmin; t.dw0 = wmin;
-    t.PH = d->SA * (TH - 1) + (hmax - hmin + 1); t.PW = d->SA * (TW - 1) + (wmax - wmin + 1);
+    const XmcTapBox b = xmc_tap_box(d, 0);
+    t.dh0 = b.hmin; t.dw0 = b.wmin;
+    t.PH = d->SA * (TH - 1) + (b.hmax - b.hmin + 1); t.PW = d->SA * (TW - 1) + (b.wmax - b.wmin + 1);
     if (s2 ? (t.PH > 18 || t.PW > 66 || (t.PW & 1)) : t16 ? (t.PH > 18 || t.PW > 18) : (t.PH > 10 || t.PW > 34)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nco = d->CD <= 16 ? 1 : (d->CD <= 32 ? 2 : 4);

@@ -33,6 +33,7 @@
 // Takes over: F.conv2d at df_gan.py:187-188 (G_Block c1/c2), 273,276 (resD conv_r) for Cin % 64 == 0 and the matching halves
 // of errD.backward() / errG.backward() (train_gan.py:228,288).
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -42,15 +43,8 @@
 
 namespace {
 
-struct WtCfg {
-    int TH, TW, log2TW;
-    int tiles_y, tiles_x;
-    int PH[XMC_MAX_CLASSES], PW[XMC_MAX_CLASSES];        // patch size per class
-    int dh0[XMC_MAX_CLASSES], dw0[XMC_MAX_CLASSES];      // min tap offsets per class (MODE 0)
-    int nslab;                                           // K slabs per tile: CS/64 (MODE 0), 4*CS/64 (MODE 1)
-    int patch_bytes;                                     // one patch buffer (max over classes), multiple of 16
-    int8_t tsel[4][4];                                   // MODE 1: tap index of (dy*2+dx, ta*2+tb)
-};
+struct WtCfg : XmcHaloPlan {};     // conv_plan.h; a type of this file, so that the kernels keep their names
+static_assert(sizeof(WtCfg) == sizeof(XmcHaloPlan), "layout of wtile2_kernel's plan argument");
 
 constexpr int kPStride = 160;       // bytes between patch pixels
 constexpr int kPIT = 12;            // patch pixels per staging thread (32 pixel rows of 8 units per pass): <= 384 pixels
@@ -485,61 +479,13 @@ __global__ __launch_bounds__(64 * CW + 256) void wtile2_kernel(const XmcConvDesc
 
 // Fills the plan; returns 1 when the descriptor is this kernel's case.
 int plan(const XmcConvDesc* d, WtCfg* t, int* mode, int* tn) {
-    if (d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16 || d->src_shift != 0) return 0;
-    if (d->CS % 64 != 0 || d->CS > 64 * 64 / 4) return 0;
     if (d->CDw % 128 == 0) *tn = 8;
     else if (d->CDw == 64 && d->CS > 64) *tn = 4;      // 64 -> 64 stays on the weights-resident kernel (conv_tile.hip)
     else return 0;
-    if (d->MW % 16 != 0) return 0;
-    const int TW = d->MW >= 32 ? 32 : 16, TH = 256 / TW;
-    if (d->MH % TH != 0 || d->MW % TW != 0) return 0;
-    t->TH = TH; t->TW = TW; t->log2TW = TW == 32 ? 5 : 4;
-    t->tiles_y = d->MH / TH; t->tiles_x = d->MW / TW;
-    int maxpix = 0;
-    if (d->SA == 1) {
-        if (d->ntaps != 9 && d->ntaps != 4) return 0;
-        *mode = 0;
-        t->nslab = d->CS / 64;
-        for (int z = 0; z < d->nclass; ++z) {
-            int hmin = 127, hmax = -128, wmin = 127, wmax = -128;
-            for (int k = 0; k < d->ntaps; ++k) {
-                const int h = d->dh[z][k], w = d->dw[z][k];
-                hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-                wmin = w < wmin ? w : wmin; wmax = w > wmax ? w : wmax;
-            }
-            // halo depth <= tile size (a halo row is outside the image only for tiles on that border)
-            if (hmin < -TH || hmax > TH || wmin < -TW || wmax > TW) return 0;
-            t->dh0[z] = hmin; t->dw0[z] = wmin;
-            t->PH[z] = TH + (hmax - hmin); t->PW[z] = TW + (wmax - wmin);
-            if (t->PH[z] * t->PW[z] > 32 * kPIT) return 0;
-            if (d->SH != d->MH || d->SW != d->MW) return 0;
-            maxpix = t->PH[z] * t->PW[z] > maxpix ? t->PH[z] * t->PW[z] : maxpix;
-        }
-    } else if (d->SA == 2) {
-        if (d->ntaps != 16 || d->nclass != 1 || d->DA != 1 || d->SH != 2 * d->MH || d->SW != 2 * d->MW) return 0;
-        *mode = 1;
-        t->nslab = 4 * (d->CS / 64);
-        if (t->nslab > 64) return 0;
-        for (int g = 0; g < 4; ++g)
-            for (int tp = 0; tp < 4; ++tp) {
-                const int wh = 2 * (tp >> 1) + (g >> 1) - 1, ww = 2 * (tp & 1) + (g & 1) - 1;
-                int found = -1;
-                for (int k = 0; k < 16; ++k)
-                    if (d->dh[0][k] == wh && d->dw[0][k] == ww) found = found < 0 ? k : 99;
-                if (found < 0 || found > 15) return 0;
-                t->tsel[g][tp] = (int8_t)found;
-            }
-        t->PH[0] = TH + 1; t->PW[0] = TW + 1; t->dh0[0] = t->dw0[0] = 0;
-        maxpix = t->PH[0] * t->PW[0];
-        if (maxpix > 32 * kPIT) return 0;
-    } else {
-        return 0;
-    }
-    if (d->dst_pool && (d->DA != 1 || d->nclass != 1 || (d->DH & 1) || (d->DW & 1))) return 0;
-    if (d->res_mode == 2 && d->DA != 1) return 0;
+    if (!xmc_halo_plan(d, t, mode, 1)) return 0;
+    const int maxpix = xmc_halo_max_patch(d, t);
+    if (maxpix > 32 * kPIT) return 0;                  // staging registers
     t->patch_bytes = (maxpix * kPStride + 15) & ~15;
-    // 32-bit unit offsets in the kernel
-    if ((int64_t)d->N * d->SH * d->SW * (d->CS / 8) >= (1ll << 31) || (int64_t)d->N * d->DH * d->DW * (d->CD / 8) >= (1ll << 31)) return 0;
     return 1;
 }
 
@@ -553,38 +499,26 @@ int launch(const XmcConvDesc& d, const WtCfg& t, hipStream_t st) {
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
     gx = xmc_ab_grid(gx);
-    // epilogue option sets of the training step as compile-time instantiations (common.h: kEpi*)
+    const dim3 grid((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), block(64 * CW + 256);
+    const XmcKName name = {"wtile2_kernel<%d, %d, %d, %d>", {NTAPS, MODE, TN, CW}};
+    // epilogue option sets of the training step as compile-time instantiations (common.h: the kEpi* lists)
+    constexpr auto sets = [] {
+        if constexpr (NTAPS == 9 && TN == 8) return kEpiBlockEnd + kEpiPlain;
+        else if constexpr (NTAPS == 9) return kEpiPlain;
+        else if constexpr (MODE == 1 && TN == 8) return kEpiStride2;
+        else if constexpr (NTAPS == 4 && MODE == 0) return kEpiClasses;
+        else return XmcEpiList<>{};
+    }();
     static const bool no_epi = xmc_debug_off("no_wtile_epi");
     const int epi = no_epi ? -1 : xmc_epi_mask(d);
-#define XMC_W2_EPI(E)                                                                                                                          \
-    if (epi == (E)) {                                                                                                                          \
-        XMC_ALLOW_BIG_LDS((wtile2_kernel<NTAPS, MODE, TN, CW, (E)>));                                                                          \
-        hipLaunchKernelGGL((wtile2_kernel<NTAPS, MODE, TN, CW, (E)>), dim3((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), dim3(64 * CW + 256), lds, st, \
-                           d, t, ntiles);                                                                                                      \
-        xmc_note_kernel("wtile2_kernel<%d, %d, %d, %d>", NTAPS, MODE, TN, CW);                                                                 \
-        XMC_LAUNCH_CHECK();                                                                                                                    \
-        return 0;                                                                                                                              \
-    }
-    if constexpr (NTAPS == 9 && TN == 8) {
-        XMC_W2_EPI(kEpiGSum) XMC_W2_EPI(kEpiDKeep) XMC_W2_EPI(kEpiDFwd) XMC_W2_EPI(kEpiDLast) XMC_W2_EPI(kEpiMask) XMC_W2_EPI(0) XMC_W2_EPI(kEpiDLin)
-        XMC_W2_EPI(kEpiDKeepS) XMC_W2_EPI(kEpiDLastS) XMC_W2_EPI(kEpiDgDot)
-        XMC_W2_EPI(kEpiBias) XMC_W2_EPI(kEpiBias | kEpiLrelu)            // the attention-modulation blocks' convolutions
-    } else if constexpr (NTAPS == 9) {
-        XMC_W2_EPI(kEpiBias) XMC_W2_EPI(kEpiBias | kEpiLrelu) XMC_W2_EPI(0)
-    } else if constexpr (MODE == 1 && TN == 8) {
-        XMC_W2_EPI(kEpiLrelu) XMC_W2_EPI(0) XMC_W2_EPI(kEpiMask)
-    } else if constexpr (NTAPS == 4 && MODE == 0) {
-        XMC_W2_EPI(kEpiRes) XMC_W2_EPI(kEpiBias) XMC_W2_EPI(0)
-    }
-#undef XMC_W2_EPI
+    int rc;
+    if (xmc_epi_launch(sets, epi, &rc, [&](auto e) {
+            return xmc_launch<&wtile2_kernel<NTAPS, MODE, TN, CW, decltype(e)::value>>(grid, block, lds, st, name, d, t, ntiles);
+        }))
+        return rc;
     if (d.sign_bits || d.dot) return 1;          // only the compile-time sets above carry these two; the next kernel in line takes it
     xmc_note_generic_epi(NTAPS == 9 ? (TN == 8 ? "wtile2<9,0,8>" : "wtile2<9,0,4>") : MODE == 1 ? (TN == 8 ? "wtile2<4,1,8>" : "wtile2<4,1,4>") : "wtile2<4,0>", xmc_epi_mask(d));
-    XMC_ALLOW_BIG_LDS((wtile2_kernel<NTAPS, MODE, TN, CW>));
-    hipLaunchKernelGGL((wtile2_kernel<NTAPS, MODE, TN, CW>), dim3((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), dim3(64 * CW + 256), lds, st, d, t,
-                       ntiles);
-    xmc_note_kernel("wtile2_kernel<%d, %d, %d, %d>", NTAPS, MODE, TN, CW);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    return xmc_launch<&wtile2_kernel<NTAPS, MODE, TN, CW>>(grid, block, lds, st, name, d, t, ntiles);
 }
 
 }  // namespace

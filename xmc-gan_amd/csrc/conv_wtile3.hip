@@ -33,21 +33,17 @@
 // Takes over: F.conv2d at df_gan.py:187-188 (G_Block c1/c2), 273,276 (resD conv_r) for the wide layers and the matching halves of
 // errD.backward() / errG.backward() (train_gan.py:228,288).
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-struct W3Cfg {
-    int TH, TW, log2TW;
-    int tiles_y, tiles_x;
-    int PH[XMC_MAX_CLASSES], PW[XMC_MAX_CLASSES];        // patch size per class
-    int dh0[XMC_MAX_CLASSES], dw0[XMC_MAX_CLASSES];      // min tap offsets per class (MODE 0)
-    int nslab;                                           // K slabs per tile: CS/64 (MODE 0), 4*CS/64 (MODE 1)
-    int patch_bytes;                                     // one patch buffer: 384 pixel slots x 128 B
-    int8_t tsel[4][4];                                   // MODE 1: tap index of (dy*2+dx, ta*2+tb)
+struct W3Cfg : XmcHaloPlan {                             // conv_plan.h; patch_bytes: 376 pixel slots x 128 B
     int ipt;                                             // images per tile: 1, or 4 (8 x 8 maps: a tile is four whole images side by side)
 };
+// W3Cfg is a kernel argument: ipt is its only own member, so these two sizes put it at offset 108, right behind the shared plan
+static_assert(sizeof(W3Cfg) == 112 && sizeof(W3Cfg) == sizeof(XmcHaloPlan) + sizeof(int), "layout of wtile3_kernel's plan argument");
 
 constexpr int kPI = 6;              // 1 KB patch pieces (8 pixels x 128 B) per wave and slab, at most
 constexpr int kPieces = 47;         // pieces of a patch buffer: 376 pixel slots (10 x 34 = 340 pixels; four 8 x 8 images with their halos, 10 x 37 = 370)
@@ -527,70 +523,34 @@ __global__ __launch_bounds__(512) void wtile3_kernel(const XmcConvDesc d, const 
 
 // Fills the plan; returns 1 when the descriptor is this kernel's case.
 int plan3(const XmcConvDesc* d, W3Cfg* t, int* mode, int* wm) {
-    if (d->dtype != XMC_BF16 || d->out_dtype != XMC_BF16 || d->src_shift != 0) return 0;
-    if (d->CS % 64 != 0 || d->CS > 64 * 64 / 4) return 0;
     if (d->CDw % 256 == 0) *wm = 2;
     else if (d->CDw % 128 == 0) *wm = 4;
     else return 0;
     // 8 x 8 maps (the last discriminator blocks, the generator's second block): a tile is four whole images side by side
     static const bool no_mi = xmc_debug_off("no_wtile3_multi_image");
     const bool mi = !no_mi && d->MW == 8 && d->MH == 8 && d->N % 4 == 0;
-    if (!mi && d->MW % 16 != 0) return 0;
-    const int TW = (mi || d->MW >= 32) ? 32 : 16, TH = 256 / TW;
-    if (!mi && (d->MH % TH != 0 || d->MW % TW != 0)) return 0;
-    t->TH = TH; t->TW = TW; t->log2TW = TW == 32 ? 5 : 4;
-    t->tiles_y = mi ? 1 : d->MH / TH; t->tiles_x = mi ? 1 : d->MW / TW;
     t->ipt = mi ? 4 : 1;
+    if (!xmc_halo_plan(d, t, mode, t->ipt)) return 0;
     int maxpix = 0;
-    if (d->SA == 1) {
-        if (d->ntaps != 9 && d->ntaps != 4) return 0;
-        *mode = 0;
-        t->nslab = d->CS / 64;
-        for (int z = 0; z < d->nclass; ++z) {
-            int hmin = 127, hmax = -128, wmin = 127, wmax = -128;
-            for (int k = 0; k < d->ntaps; ++k) {
-                const int h = d->dh[z][k], w = d->dw[z][k];
-                hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-                wmin = w < wmin ? w : wmin; wmax = w > wmax ? w : wmax;
-            }
-            if (hmin < -TH || hmax > TH || wmin < -TW || wmax > TW) return 0;
-            t->dh0[z] = hmin; t->dw0[z] = wmin;
-            t->PH[z] = TH + (hmax - hmin); t->PW[z] = TW + (wmax - wmin);
-            if (mi) {
-                // image k's columns start at patch column 9 k - dw0; one shared zero column between neighbours
-                if (wmax - wmin < 1 || wmax - wmin > 2 || wmin > 0 || wmax < 0 || hmin > 0 || hmax < 0) return 0;
-                t->PW[z] = 36 + (wmax - wmin == 2 ? 1 : 0);
-                // rows below the declared patch are only ever read as zeros: every slot past the patch is zero-filled on each fill, so
-                // the bottom halo row may (and, for 3x3, does: 10 x 37 = 370 > 368) reach into the last piece
-                if (t->PH[z] * t->PW[z] > kPieces * 8 || (hmax > 0 ? (t->PH[z] - 1) * t->PW[z] : t->PH[z] * t->PW[z]) > (kPieces - 1) * 8) return 0;
-            }
-            if (d->SH != d->MH || d->SW != d->MW) return 0;
-            if (!mi) maxpix = t->PH[z] * t->PW[z] > maxpix ? t->PH[z] * t->PW[z] : maxpix;
-        }
-    } else if (d->SA == 2) {
-        if (d->ntaps != 16 || d->nclass != 1 || d->DA != 1 || d->SH != 2 * d->MH || d->SW != 2 * d->MW) return 0;
-        *mode = 1;
-        t->nslab = 4 * (d->CS / 64);
-        if (t->nslab > 64) return 0;
-        for (int g = 0; g < 4; ++g)
-            for (int tp = 0; tp < 4; ++tp) {
-                const int wh = 2 * (tp >> 1) + (g >> 1) - 1, ww = 2 * (tp & 1) + (g & 1) - 1;
-                int found = -1;
-                for (int k = 0; k < 16; ++k)
-                    if (d->dh[0][k] == wh && d->dw[0][k] == ww) found = found < 0 ? k : 99;
-                if (found < 0 || found > 15) return 0;
-                t->tsel[g][tp] = (int8_t)found;
-            }
-        t->PH[0] = TH + 1; t->PW[0] = mi ? 36 : TW + 1; t->dh0[0] = t->dw0[0] = 0;
+    if (!mi) {
+        maxpix = xmc_halo_max_patch(d, t);
+    } else if (*mode == 1) {
+        t->PW[0] = 36;
         maxpix = t->PH[0] * t->PW[0];
     } else {
-        return 0;
+        for (int z = 0; z < d->nclass; ++z) {
+            const XmcTapBox b = xmc_tap_box(d, z);
+            const int ww = b.wmax - b.wmin;
+            // image k's columns start at patch column 9 k - dw0; one shared zero column between neighbours
+            if (ww < 1 || ww > 2 || b.wmin > 0 || b.wmax < 0 || b.hmin > 0 || b.hmax < 0) return 0;
+            t->PW[z] = 36 + (ww == 2 ? 1 : 0);
+            // rows below the declared patch are only ever read as zeros: every slot past the patch is zero-filled on each fill, so
+            // the bottom halo row may (and, for 3x3, does: 10 x 37 = 370 > 368) reach into the last piece
+            if (t->PH[z] * t->PW[z] > kPieces * 8 || (b.hmax > 0 ? (t->PH[z] - 1) * t->PW[z] : t->PH[z] * t->PW[z]) > (kPieces - 1) * 8) return 0;
+        }
     }
     if (maxpix > (kPieces - 1) * 8) return 0;      // the last piece must stay past the end of every patch (patch_piece)
-    if (d->dst_pool && (d->DA != 1 || d->nclass != 1 || (d->DH & 1) || (d->DW & 1))) return 0;
-    if (d->res_mode == 2 && d->DA != 1) return 0;
     t->patch_bytes = kPatchSlots * 128;
-    if ((int64_t)d->N * d->SH * d->SW * (d->CS / 8) >= (1ll << 31) || (int64_t)d->N * d->DH * d->DW * (d->CD / 8) >= (1ll << 31)) return 0;
     return 1;
 }
 
@@ -604,33 +564,24 @@ int launch3(const XmcConvDesc& d, const W3Cfg& t, hipStream_t st) {
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
     gx = xmc_ab_grid(gx);
-    // epilogue option sets of the training step as compile-time instantiations (common.h: kEpi*)
+    const dim3 grid((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), block(512);
+    const XmcKName name = {"wtile3_kernel<%d, %d, %d>", {NTAPS, MODE, WM}};
+    // epilogue option sets of the training step as compile-time instantiations (common.h: the kEpi* lists)
+    constexpr auto sets = [] {
+        if constexpr (NTAPS == 9) return kEpiBlockEnd + XmcEpiList<0>{};
+        else if constexpr (MODE == 1) return kEpiStride2;
+        else return kEpiClasses;
+    }();
     static const bool no_epi = xmc_debug_off("no_wtile_epi");
     const int epi = no_epi ? -1 : xmc_epi_mask(d);
-#define XMC_W3_EPI(E)                                                                                                                        \
-    if (epi == (E)) {                                                                                                                        \
-        XMC_ALLOW_BIG_LDS((wtile3_kernel<NTAPS, MODE, WM, (E)>));                                                                            \
-        hipLaunchKernelGGL((wtile3_kernel<NTAPS, MODE, WM, (E)>), dim3((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), dim3(512), lds, st, d, t, ntiles); \
-        xmc_note_kernel("wtile3_kernel<%d, %d, %d>", NTAPS, MODE, WM);                                                                       \
-        XMC_LAUNCH_CHECK();                                                                                                                  \
-        return 0;                                                                                                                            \
-    }
-    if constexpr (NTAPS == 9) {
-        XMC_W3_EPI(kEpiGSum) XMC_W3_EPI(kEpiDKeep) XMC_W3_EPI(kEpiDFwd) XMC_W3_EPI(kEpiDLast) XMC_W3_EPI(kEpiMask) XMC_W3_EPI(0) XMC_W3_EPI(kEpiDLin)
-        XMC_W3_EPI(kEpiDKeepS) XMC_W3_EPI(kEpiDLastS) XMC_W3_EPI(kEpiDgDot)
-    } else if constexpr (MODE == 1) {
-        XMC_W3_EPI(kEpiLrelu) XMC_W3_EPI(0) XMC_W3_EPI(kEpiMask)       // forward; data gradient of the fused upsample conv; MA-GP's linearised forward
-    } else {
-        XMC_W3_EPI(kEpiRes) XMC_W3_EPI(kEpiBias) XMC_W3_EPI(0)
-    }
-#undef XMC_W3_EPI
+    int rc;
+    if (xmc_epi_launch(sets, epi, &rc, [&](auto e) {
+            return xmc_launch<&wtile3_kernel<NTAPS, MODE, WM, decltype(e)::value>>(grid, block, lds, st, name, d, t, ntiles);
+        }))
+        return rc;
     if (d.sign_bits || d.dot) return 1;          // only the compile-time sets above carry these two; the next kernel in line takes it
     xmc_note_generic_epi(NTAPS == 9 ? "wtile3<9,0>" : MODE == 1 ? "wtile3<4,1>" : "wtile3<4,0>", epi);
-    XMC_ALLOW_BIG_LDS((wtile3_kernel<NTAPS, MODE, WM>));
-    hipLaunchKernelGGL((wtile3_kernel<NTAPS, MODE, WM>), dim3((unsigned)gx, (unsigned)ny, (unsigned)d.nclass), dim3(512), lds, st, d, t, ntiles);
-    xmc_note_kernel("wtile3_kernel<%d, %d, %d>", NTAPS, MODE, WM);
-    XMC_LAUNCH_CHECK();
-    return 0;
+    return xmc_launch<&wtile3_kernel<NTAPS, MODE, WM>>(grid, block, lds, st, name, d, t, ntiles);
 }
 
 }  // namespace
