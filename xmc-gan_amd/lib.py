@@ -19,6 +19,7 @@ ACT_NONE, ACT_LRELU, ACT_TANH, ACT_RELU = 0, 1, 2, 3
 MAX_TAPS, MAX_CLASSES = 16, 4
 POOL_MAX, POOL_AVG_VALID, POOL_AVG_PAD = 0, 1, 2     # xmc_pool3x3 modes
 DIFFAUG_PARTS = 64        # XMC_DIFFAUG_PARTS: partials per image of xmc_diffaug_sums and xmc_image_minmax
+BIAS_REPLICAS = 16        # XMC_BIAS_REPLICAS: rows of the bias-gradient accumulator of xmc_conv_wgrad and xmc_gtail_bwd
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 

@@ -53,6 +53,114 @@ class ConvGeom:
         return self._perm_dev
 
 
+# ------------------------------------------------------------------------------------------ tap tables and descriptors
+# What the convolution kernels compute, as integers (the index space: include/xmc_gan_hip.h above XmcConvDesc); tests/test_conv_desc_cpu.py
+# executes these descriptors against torch without a GPU.  A tap table is a list of classes [(dph, dpw, [(dh, dw, weight slice), ...]), ...].
+def _fwd_classes(geom, taps=None):
+    """forward: `geom.taps()`, or its range ``taps`` = (lo, hi), as one class"""
+    table = geom.taps() if taps is None else geom.taps()[taps[0]:taps[1]]
+    assert 1 <= len(table) <= L.MAX_TAPS, (geom.kh, geom.kw, taps)
+    return [(0, 0, table)]
+
+
+def _dgrad_classes(geom):
+    """data gradient: one class per parity (ph, pw) of the input pixel, holding the taps whose stride lands on it; slices transposed"""
+    s, k, p = geom.s, geom.k, geom.p
+    assert k is not None and p is not None and k % s == 0 and k * k <= L.MAX_TAPS, "data gradient: square kernel, k % s == 0"
+    classes = [(ph, pw, [((ph + p - kh) // s, (pw + p - kw) // s, kh * k + kw) for kh in range(k) if (ph + p - kh) % s == 0
+                         for kw in range(k) if (pw + p - kw) % s == 0]) for ph in range(s) for pw in range(s)]
+    assert len({len(taps) for _, _, taps in classes}) == 1
+    return classes
+
+
+def _upconv_fwd_classes():
+    """conv3x3(nearest_up2(x)): output parity (i, j) reads a 2x2 neighbourhood of x through the pre-summed slices (i*2+j)*4 + th*2+tw"""
+    return [(i, j, [(i - 1 + th, j - 1 + tw, (i * 2 + j) * 4 + th * 2 + tw) for th in range(2) for tw in range(2)])
+            for i in range(2) for j in range(2)]
+
+
+def _upconv_dgrad_classes():
+    """its adjoint: a stride-2 gather of 16 taps over dy, slice (i, j, th, tw) from the output pixel of parity (i, j) it fed"""
+    return [(0, 0, [(i - 2 * (i - 1 + th), j - 2 * (j - 1 + tw), (i * 2 + j) * 4 + th * 2 + tw)
+                    for i in range(2) for th in range(2) for j in range(2) for tw in range(2)])]
+
+
+def _fill_taps(d, cls, taps):
+    for t, (dh, dw, wi) in enumerate(taps):
+        d.dh[cls][t] = dh
+        d.dw[cls][t] = dw
+        d.wi[cls][t] = wi
+
+
+def _conv_desc(N, src, dst, m, SA, DA, CDw, dtype, out_dtype, classes, src_shift=0, groups=0):
+    """a fresh XmcConvDesc, geometry and tap fields written, pointers null; src = (SH, SW, CS), dst = (DH, DW, CD), m = (MH, MW), dtype codes"""
+    d = L.ConvDesc()
+    d.N, (d.SH, d.SW, d.CS), (d.DH, d.DW, d.CD), (d.MH, d.MW) = N, src, dst, m
+    d.SA, d.DA, d.src_shift, d.ntaps, d.nclass, d.CDw = SA, DA, src_shift, len(classes[0][2]), len(classes), CDw
+    d.dtype, d.out_dtype, d.groups = dtype, out_dtype, groups
+    for z, (dph, dpw, taps) in enumerate(classes):
+        _fill_taps(d, z, taps)
+        d.dph[z], d.dpw[z] = dph, dpw
+    return d
+
+
+def _fwd_desc(geom, N, H, W, CS, dtype, out_dtype, up=False, taps=None):
+    """y [N,OH,OW,pad8(cout)] = conv(x [N,H,W,CS]); ``up``: x is read through a nearest x2 (src_shift); ``taps``: a range of the table"""
+    sh = 1 if up else 0
+    OH, OW = geom.out_hw(H << sh, W << sh)
+    return _conv_desc(N, (H, W, CS), (OH, OW, pad_to(geom.cout, 8)), (OH, OW), geom.s, 1, pad_to(geom.cout, 32), dtype, out_dtype,
+                      _fwd_classes(geom, taps), sh, geom.groups)
+
+
+def _dgrad_geom_desc(geom, N, OH, OW, CDy, H, W, CDx, dtype, out_dtype):
+    """dx [N,H,W,CDx] from dy [N,OH,OW,CDy]: the index space is one parity class of dx, [H/s, W/s]"""
+    classes, s = _dgrad_classes(geom), geom.s
+    assert H % s == 0 and W % s == 0
+    return _conv_desc(N, (OH, OW, CDy), (H, W, CDx), (H // s, W // s), 1, s, pad_to(geom.cin, 32), dtype, out_dtype, classes, 0, geom.groups)
+
+
+def _wgrad_desc(geom, N, H, W, CS, OH, OW, CDy, dtype, up=False):
+    """the forward table over x [N,H,W,CS] as `src` and dy [N,OH,OW,CDy] as `dst`; CDw: the rows of a packed dW slice"""
+    return _conv_desc(N, (H, W, CS), (OH, OW, CDy), (OH, OW), geom.s, 1, pad_to(CDy, 32), dtype, L.F32, _fwd_classes(geom),
+                      1 if up else 0, geom.groups)
+
+
+def _upconv_fwd_desc(geom, N, H, W, CS, dtype, out_dtype):
+    assert geom.k == 3 and geom.s == 1 and geom.p == 1
+    return _conv_desc(N, (H, W, CS), (2 * H, 2 * W, pad_to(geom.cout, 8)), (H, W), 1, 2, pad_to(geom.cout, 32), dtype, out_dtype,
+                      _upconv_fwd_classes())
+
+
+def _upconv_dgrad_desc(geom, N, OH, OW, CDy, CDx, dtype, out_dtype):
+    H, W = OH // 2, OW // 2
+    return _conv_desc(N, (OH, OW, CDy), (H, W, CDx), (H, W), 2, 1, pad_to(geom.cin, 32), dtype, out_dtype, _upconv_dgrad_classes())
+
+
+def _bind(d, src, wpk, dst, bias=None):
+    """the operand pointers of a forward / data-gradient launch; the packed weights must have the slice rows the builder wrote"""
+    assert wpk.shape[1] == d.CDw, (wpk.shape, d.CDw)
+    d.src, d.wpk, d.dst = src.data_ptr(), wpk.data_ptr(), dst.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+
+
+_IGEMM = "igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)"
+_WGRAD = "wgrad_kernel (conv weight gradient, MFMA + split-K atomics)"
+
+
+def _conv_launch(family, flops, kind, dtype, N, H, W, geom, nbytes):
+    """the `prof.launch` record of one convolution launch, tagged "<kind> <dtype> N.. HxW cin->cout k..s..\""""
+    return prof.launch(family, flops, f"{kind} {dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k or f'{geom.kh}x{geom.kw}'}s{geom.s}", nbytes)
+
+
+def _try_launch(name, *args):
+    """an entry point that may decline its case: True when it launched, False on return code 1, anything else raises (L.check)"""
+    rc = getattr(L.load(), name)(*args)
+    if rc == 1:
+        return False
+    L.check(rc, name)
+    return True
+
+
 def _igemm(d, what):
     """xmc_conv_igemm, handing over the split-K scratch the descriptor asks for (the layers on 4x4 / 8x8 maps: XmcConvDesc.splitk_ws).
     The scratch is a plain caching-allocator block: stream order keeps it alive until the two launches that use it have run."""
@@ -62,13 +170,6 @@ def _igemm(d, what):
         ws = torch.empty(nb, dtype=torch.uint8, device=torch.cuda.current_device())
         d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), nb
     L.check(lib.xmc_conv_igemm(C.byref(d), _st()), what)
-
-
-def _fill_taps(d, cls, taps):
-    for t, (dh, dw, wi) in enumerate(taps):
-        d.dh[cls][t] = dh
-        d.dw[cls][t] = dw
-        d.wi[cls][t] = wi
 
 
 _pack_cache = {}          # (id(param), kind, transpose, dtype) -> _PackEntry
@@ -141,10 +242,6 @@ def _packed_cached(w, geom, transpose, dtype, up=False, lo=False):
         _retired_packs.append(hit.out)        # a captured graph may still write / read the buffer it saw
     _pack_cache[k] = e
     return e.out
-
-
-def _packed_upconv_cached(w, geom, transpose, dtype):
-    return _packed_cached(w, geom, transpose, dtype, up=True)
 
 
 _graphs_alive = [0]       # set by graph.GraphedIteration: pack buffers a capture has seen must outlive it
@@ -230,26 +327,13 @@ def _upconv_fwd_raw(x, w, bias, geom, act, out_dtype):
     """conv3x3(nearest_up2(x), w) + bias on the LOW-resolution x [N,H,W,Cs] -> [N,2H,2W,Cd]: four output-parity classes,
     each a 2x2-tap convolution with pre-summed weights (4/9 of the MACs, the upsampled tensor never exists)."""
     _need_cuda(x, w)
-    assert geom.k == 3 and geom.s == 1 and geom.p == 1
     N, H, W, CS = x.shape
-    cd_p = pad_to(geom.cout, 8)
-    wpk = _packed_upconv_cached(w, geom, 0, x.dtype)
-    y = torch.empty((N, 2 * H, 2 * W, cd_p), dtype=out_dtype, device=x.device)
-    d = L.ConvDesc()
-    d.src, d.wpk, d.dst = x.data_ptr(), wpk.data_ptr(), y.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.N, d.SH, d.SW, d.CS = N, H, W, CS
-    d.DH, d.DW, d.CD = 2 * H, 2 * W, cd_p
-    d.MH, d.MW, d.SA, d.DA, d.src_shift = H, W, 1, 2, 0
-    d.ntaps, d.nclass, d.CDw = 4, 4, wpk.shape[1]
-    d.act, d.dtype, d.out_dtype = act, _code(x.dtype), _code(out_dtype)
-    for i in range(2):
-        for j in range(2):
-            cls = i * 2 + j
-            _fill_taps(d, cls, [(i - 1 + th, j - 1 + tw, cls * 4 + th * 2 + tw) for th in range(2) for tw in range(2)])
-            d.dph[cls], d.dpw[cls] = i, j
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * 4 * H * W * geom.cout * geom.cin * 9,
-                     f"upconv-fwd {x.dtype} N{N} {2 * H}x{2 * W} {geom.cin}->{geom.cout} k3s1", _nbytes(x, wpk, y)):
+    d = _upconv_fwd_desc(geom, N, H, W, CS, _code(x.dtype), _code(out_dtype))
+    wpk = _packed_cached(w, geom, 0, x.dtype, up=True)
+    y = torch.empty((N, d.DH, d.DW, d.CD), dtype=out_dtype, device=x.device)
+    _bind(d, x, wpk, y, bias)
+    d.act = act
+    with _conv_launch(_IGEMM, 2.0 * N * 4 * H * W * geom.cout * geom.cin * 9, "upconv-fwd", x.dtype, N, 2 * H, 2 * W, geom, _nbytes(x, wpk, y)):
         _igemm(d, "xmc_conv_igemm(upconv fwd)")
     return y
 
@@ -259,28 +343,11 @@ def _upconv_dgrad_raw(dy, w, geom, in_dtype):
     pre-summed weight slices (transposed)."""
     _need_cuda(dy, w)
     N, OH, OW, CDy = dy.shape
-    H, W = OH // 2, OW // 2
-    cs_p = chan_pad(geom.cin, in_dtype)
-    wpk = _packed_upconv_cached(w, geom, 1, dy.dtype)
-    dx = torch.empty((N, H, W, cs_p), dtype=in_dtype, device=dy.device)
-    d = L.ConvDesc()
-    d.src, d.wpk, d.dst = dy.data_ptr(), wpk.data_ptr(), dx.data_ptr()
-    d.N, d.SH, d.SW, d.CS = N, OH, OW, CDy
-    d.DH, d.DW, d.CD = H, W, cs_p
-    d.MH, d.MW, d.SA, d.DA, d.src_shift = H, W, 2, 1, 0
-    d.ntaps, d.nclass, d.CDw = 16, 1, wpk.shape[1]
-    d.act, d.dtype, d.out_dtype = L.ACT_NONE, _code(dy.dtype), _code(in_dtype)
-    taps = []
-    for i in range(2):
-        for th in range(2):
-            ro = i - 2 * (i - 1 + th)
-            for j in range(2):
-                for tw in range(2):
-                    co = j - 2 * (j - 1 + tw)
-                    taps.append((ro, co, (i * 2 + j) * 4 + th * 2 + tw))
-    _fill_taps(d, 0, taps)
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * 9,
-                     f"upconv-dgrad {dy.dtype} N{N} {OH}x{OW} {geom.cin}->{geom.cout} k3s1", _nbytes(dy, wpk, dx)):
+    d = _upconv_dgrad_desc(geom, N, OH, OW, CDy, chan_pad(geom.cin, in_dtype), _code(dy.dtype), _code(in_dtype))
+    wpk = _packed_cached(w, geom, 1, dy.dtype, up=True)
+    dx = torch.empty((N, d.DH, d.DW, d.CD), dtype=in_dtype, device=dy.device)
+    _bind(d, dy, wpk, dx)
+    with _conv_launch(_IGEMM, 2.0 * N * OH * OW * geom.cout * geom.cin * 9, "upconv-dgrad", dy.dtype, N, OH, OW, geom, _nbytes(dy, wpk, dx)):
         _igemm(d, "xmc_conv_igemm(upconv dgrad)")
     return dx
 
@@ -294,34 +361,18 @@ def _conv_fwd_raw(x, w, bias, geom, act, out_dtype, res=None, alpha=None, up=Fal
     kernel (XmcConvDesc.sc_img, xmc_conv_ptile_scimg) -- returns None when the kernel declines the shape.
     ``taps`` = (lo, hi): only that range of the tap table, for a kernel of more than MAX_TAPS taps (the caller sums the ranges through ``res``)."""
     _need_cuda(x, w)
-    table = geom.taps() if taps is None else geom.taps()[taps[0]:taps[1]]
-    assert 1 <= len(table) <= L.MAX_TAPS, (geom.kh, geom.kw, taps)
     N, H, W, CS = x.shape
-    sh = 1 if up else 0
-    Hv, Wv = H << sh, W << sh
-    OH, OW = geom.out_hw(Hv, Wv)
-    cd_p = pad_to(geom.cout, 8)
+    d = _fwd_desc(geom, N, H, W, CS, _code(x.dtype), _code(out_dtype), up, taps)
+    OH, OW, cd_p = d.DH, d.DW, d.CD
     assert CS == chan_pad(geom.cin, x.dtype), (CS, geom.cin)
     wpk = _packed_cached(w, geom, 0, x.dtype, lo=w_lo)      # (w_lo: the low half of the weight pair, PairConvFn)
-    if out is None:
-        y = torch.empty((N, OH, OW, cd_p), dtype=out_dtype, device=x.device)
-    else:                          # caller-provided destination
-        assert tuple(out.shape) == (N, OH, OW, cd_p) and out.dtype == out_dtype and out.is_contiguous() and out.device == x.device
-        y = out
-    d = L.ConvDesc()
-    d.src, d.wpk, d.dst = x.data_ptr(), wpk.data_ptr(), y.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
+    y = torch.empty((N, OH, OW, cd_p), dtype=out_dtype, device=x.device) if out is None else out          # or the caller's destination
+    assert tuple(y.shape) == (N, OH, OW, cd_p) and y.dtype == out_dtype and y.is_contiguous() and y.device == x.device
+    _bind(d, x, wpk, y, bias)
     d.res = res.data_ptr() if res is not None else None
     d.alpha_dev = alpha.data_ptr() if alpha is not None else None
-    d.N, d.SH, d.SW, d.CS = N, H, W, CS
-    d.DH, d.DW, d.CD = OH, OW, cd_p
-    d.MH, d.MW, d.SA, d.DA, d.src_shift = OH, OW, geom.s, 1, sh
-    d.ntaps, d.nclass, d.CDw = len(table), 1, wpk.shape[1]
-    d.act, d.dtype, d.out_dtype = act, _code(x.dtype), _code(out_dtype)
-    d.res_mode, d.round_act = res_mode, int(bool(round_act))
-    d.groups = geom.groups
+    d.act, d.res_mode, d.round_act = act, res_mode, int(bool(round_act))
     d.post_act = post_act           # applied last, to the sum with the residual (XmcConvDesc.post_act)
-    _fill_taps(d, 0, table)
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() >= cd_p, "bias must be f32 and padded to the stored channels"
     if res is not None:
@@ -349,15 +400,11 @@ def _conv_fwd_raw(x, w, bias, geom, act, out_dtype, res=None, alpha=None, up=Fal
         img, frag, sbias = sc_img
         assert res is None and tuple(img.shape) == (N, 2 * OH, 2 * OW, 8) and img.dtype == x.dtype and img.is_contiguous()
         d.sc_img, d.sc_frag, d.sc_bias = img.data_ptr(), frag.data_ptr(), sbias.data_ptr()
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * (geom.cin * geom.k * geom.k + 48),
-                         f"fwd+sc {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, wpk, img, *outs)):
-            rc = L.load().xmc_conv_ptile_scimg(C.byref(d), _st())
-        if rc == 1:
-            return None
-        L.check(rc, "xmc_conv_ptile_scimg")
-        return y if len(outs) == 1 else tuple(outs)
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * len(table),
-                     f"fwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k or f'{geom.kh}x{geom.kw}'}s{geom.s}", _nbytes(x, wpk, res, mask, *outs)):
+        flops = 2.0 * N * OH * OW * geom.cout * (geom.cin * geom.k * geom.k + 48)
+        with _conv_launch(_IGEMM, flops, "fwd+sc", x.dtype, N, H, W, geom, _nbytes(x, wpk, img, *outs)):
+            launched = _try_launch("xmc_conv_ptile_scimg", C.byref(d), _st())
+        return None if not launched else y if len(outs) == 1 else tuple(outs)
+    with _conv_launch(_IGEMM, 2.0 * N * OH * OW * geom.cout * geom.cin * d.ntaps, "fwd", x.dtype, N, H, W, geom, _nbytes(x, wpk, res, mask, *outs)):
         _igemm(d, "xmc_conv_igemm(fwd)")
     return y if len(outs) == 1 else tuple(outs)
 
@@ -372,22 +419,12 @@ def _conv1x1_pair_raw(x, w, bias, geom, out_dtype):
     if "no_pw1x1_split" not in _DEBUG_DISPATCH:
         wpk, wlo = _packed_cached(w, geom, 0, x.dtype), _packed_cached(w, geom, 0, x.dtype, lo=True)
         y = torch.empty((N, H, W, cd_p), dtype=out_dtype, device=x.device)
-        d = L.ConvDesc()
-        d.src, d.wpk, d.wpk_lo, d.dst = x.data_ptr(), wpk.data_ptr(), wlo.data_ptr(), y.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.N, d.SH, d.SW, d.CS = N, H, W, CS
-        d.DH, d.DW, d.CD = H, W, cd_p
-        d.MH, d.MW, d.SA, d.DA, d.src_shift = H, W, 1, 1, 0
-        d.ntaps, d.nclass, d.CDw = 1, 1, wpk.shape[1]
-        d.act, d.dtype, d.out_dtype = L.ACT_NONE, _code(x.dtype), _code(out_dtype)
-        _fill_taps(d, 0, [(0, 0, 0)])
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * H * W * geom.cout * geom.cin,
-                         f"fwd-pair {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k1s1", _nbytes(x, wpk, wlo, y)):
-            rc = L.load().xmc_conv_pw1x1_split(C.byref(d), _st())
-        if rc == 0:
-            return y
-        if rc != 1:
-            L.check(rc, "xmc_conv_pw1x1_split")
+        d = _conv_desc(N, (H, W, CS), (H, W, cd_p), (H, W), 1, 1, pad_to(cd_p, 32), _code(x.dtype), _code(out_dtype), _fwd_classes(geom))
+        _bind(d, x, wpk, y, bias)
+        d.wpk_lo = wlo.data_ptr()          # (`_fwd_desc`'s index space for k1s1; `groups` stays unset: it is 1, above)
+        with _conv_launch(_IGEMM, 2.0 * N * H * W * geom.cout * geom.cin, "fwd-pair", x.dtype, N, H, W, geom, _nbytes(x, wpk, wlo, y)):
+            if _try_launch("xmc_conv_pw1x1_split", C.byref(d), _st()):
+                return y
     y32 = _conv_fwd_raw(_cast_raw(x, torch.float32), w, bias, geom, L.ACT_NONE, torch.float32)
     return _cast_raw(y32, out_dtype)
 
@@ -425,27 +462,19 @@ def _conv_dgrad_raw(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=
         # read dy (xmc_conv_pw1x1_masked_src); any other shape runs the data gradient and the mask pass separately.
         assert geom.k == 1 and geom.s == 1 and not want_sumpool and src_bits.dtype == torch.uint8 and src_bits.numel() * 8 == dy.numel()
         dym = torch.empty_like(dy)
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin,
-                         f"dgrad+srcmask {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k1s1", _nbytes(dy, wpk, dx, dym)):
-            rc = L.load().xmc_conv_pw1x1_masked_src(C.byref(d), _p(src_bits), _p(dym), 0.2, _st())
-            if rc == 1:
+        with _conv_launch(_IGEMM, 2.0 * N * OH * OW * geom.cout * geom.cin, "dgrad+srcmask", dy.dtype, N, H, W, geom, _nbytes(dy, wpk, dx, dym)):
+            if not _try_launch("xmc_conv_pw1x1_masked_src", C.byref(d), _p(src_bits), _p(dym), 0.2, _st()):
                 _igemm(d, "xmc_conv_igemm(dgrad)")
                 L.call("xmc_signmask_apply", _p(dy), _p(src_bits), _p(dym), dy.numel(), 0.2, _code(dy.dtype), _st())
-            else:
-                L.check(rc, "xmc_conv_pw1x1_masked_src")
         return dx, dym
+    flops, nbytes = 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k, _nbytes(dy, wpk, dx, mask, res, dxp)
     if staged is not None:
         d.mask_bits = staged.bits.data_ptr()
-        with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                         f"dgrad+bits {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
-            rc = L.load().xmc_conv_ptile_bits(C.byref(d), _st())
-        if rc == 0:
-            return (dx, dxp) if want_sumpool else dx
-        if rc != 1:
-            L.check(rc, "xmc_conv_ptile_bits")
+        with _conv_launch(_IGEMM, flops, "dgrad+bits", dy.dtype, N, H, W, geom, nbytes):
+            if _try_launch("xmc_conv_ptile_bits", C.byref(d), _st()):
+                return (dx, dxp) if want_sumpool else dx
         d.mask_bits, d.src = None, staged.materialised().data_ptr()
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                     f"dgrad {dy.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(dy, wpk, dx, mask, res, dxp)):
+    with _conv_launch(_IGEMM, flops, "dgrad", dy.dtype, N, H, W, geom, nbytes):
         _igemm(d, "xmc_conv_igemm(dgrad)")
     return (dx, dxp) if want_sumpool else dx
 
@@ -461,30 +490,10 @@ def _dgrad_desc(dy, w, geom, in_hw, in_dtype, mask=None, res=None, res_rows=Fals
     if cs_p % 8:
         raise RuntimeError("dgrad destination needs a channel count that is a multiple of 8")
     dx = torch.empty((N, H, W, cs_p), dtype=in_dtype, device=dy.device)
-    d = L.ConvDesc()
-    d.src, d.wpk, d.dst = dy.data_ptr(), wpk.data_ptr(), dx.data_ptr()
-    d.N, d.SH, d.SW, d.CS = N, OH, OW, CDy
-    d.DH, d.DW, d.CD = H, W, cs_p
-    s, k, p = geom.s, geom.k, geom.p
-    assert k is not None and p is not None and k % s == 0 and k * k <= L.MAX_TAPS, "data gradient: square kernel, k % s == 0"
-    d.MH, d.MW, d.SA, d.DA, d.src_shift = H // s, W // s, 1, s, 0
-    d.nclass, d.CDw = s * s, wpk.shape[1]
-    d.act, d.dtype, d.out_dtype = L.ACT_NONE, _code(dy.dtype), _code(in_dtype)
-    d.groups = geom.groups
-    assert H % s == 0 and W % s == 0
-    ntaps = None
-    for ph in range(s):
-        for pw in range(s):
-            cls = ph * s + pw
-            taps = [((ph + p - kh) // s, (pw + p - kw) // s, kh * k + kw)
-                    for kh in range(k) if (ph + p - kh) % s == 0
-                    for kw in range(k) if (pw + p - kw) % s == 0]
-            assert ntaps in (None, len(taps))
-            ntaps = len(taps)
-            _fill_taps(d, cls, taps)
-            d.dph[cls], d.dpw[cls] = ph, pw
-    d.ntaps = ntaps
-    if alpha is not None:         # dx = alpha * dgrad(dy) (f32 device scalar, applied to the accumulator)
+    d = _dgrad_geom_desc(geom, N, OH, OW, CDy, H, W, cs_p, _code(dy.dtype), _code(in_dtype))
+    _bind(d, dy, wpk, dx)
+    s = geom.s
+    if alpha is not None:        # dx = alpha * dgrad(dy) (f32 device scalar, applied to the accumulator)
         d.alpha_dev = alpha.data_ptr()
     if mask is not None:
         assert mask.shape == dx.shape and mask.dtype == dx.dtype and mask.is_contiguous()
@@ -666,34 +675,30 @@ def _conv_wgrad_raw(x, dy, geom, scale=None, up=False, want_bias=False, bias_dot
     N, H, W, CS = x.shape
     _, OH, OW, CDy = dy.shape
     assert x.dtype == dy.dtype, (x.dtype, dy.dtype)
-    rows = pad_to(CDy, 32)
-    dwp = _arena.zeros((geom.k * geom.k, rows, CS), x.device)
-    gb = _arena.zeros((16, CDy), x.device) if want_bias else None     # XMC_BIAS_REPLICAS
-    d = L.ConvDesc()
+    rows, dwp, gb = _wgrad_accums(geom, CS, CDy, x.device, want_bias)
+    d = _wgrad_desc(geom, N, H, W, CS, OH, OW, CDy, _code(x.dtype), up)
     d.src, d.dst = x.data_ptr(), dy.data_ptr()
-    d.N, d.SH, d.SW, d.CS = N, H, W, CS
-    d.DH, d.DW, d.CD = OH, OW, CDy
-    d.MH, d.MW, d.SA, d.DA, d.src_shift = OH, OW, geom.s, 1, 1 if up else 0
-    d.ntaps, d.nclass, d.CDw = geom.k * geom.k, 1, rows
-    d.dtype, d.out_dtype = _code(x.dtype), L.F32
-    d.groups = geom.groups
-    _fill_taps(d, 0, [(kh - geom.p, kw - geom.p, kh * geom.k + kw) for kh in range(geom.k) for kw in range(geom.k)])
-    rc = 1
+    flops, nbytes = 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k, _nbytes(x, dy, dwp)
+    done = False
     if staged is not None and not want_bias:
         d.mask_bits = staged.bits.data_ptr()
-        with prof.launch("wgrad_kernel (conv weight gradient, MFMA + split-K atomics)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                         f"wgrad+bits {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, dy, dwp)):
-            rc = L.load().xmc_conv_wgrad_bits(C.byref(d), _p(dwp), _st())
-        if rc not in (0, 1):
-            L.check(rc, "xmc_conv_wgrad_bits")
+        with _conv_launch(_WGRAD, flops, "wgrad+bits", x.dtype, N, H, W, geom, nbytes):
+            done = _try_launch("xmc_conv_wgrad_bits", C.byref(d), _p(dwp), _st())
         d.mask_bits = None
-    if rc == 1:
+    if not done:
         if staged is not None:
             d.dst = staged.materialised().data_ptr()
-        with prof.launch("wgrad_kernel (conv weight gradient, MFMA + split-K atomics)", 2.0 * N * OH * OW * geom.cout * geom.cin * geom.k * geom.k,
-                         f"wgrad {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout} k{geom.k}s{geom.s}", _nbytes(x, dy, dwp)):
-            L.check(L.load().xmc_conv_wgrad(C.byref(d), _p(dwp), _p(gb), _st()), "xmc_conv_wgrad")
+        with _conv_launch(_WGRAD, flops, "wgrad", x.dtype, N, H, W, geom, nbytes):
+            L.call("xmc_conv_wgrad", C.byref(d), _p(dwp), _p(gb), _st())
     return _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale, bias_dot, dot)
+
+
+def _wgrad_accums(geom, CS, CDy, device, want_bias, want_w=True):
+    """zeroed f32 accumulators of a weight-gradient launch: (rows of a packed slice, dW [k*k, rows, CS] | None, bias replicas | None)"""
+    rows = pad_to(CDy, 32)
+    dwp = _arena.zeros((geom.k * geom.k, rows, CS), device) if want_w else None
+    gb = _arena.zeros((L.BIAS_REPLICAS, CDy), device) if want_w and want_bias else None
+    return rows, dwp, gb
 
 
 def _wgrad_unpack(dwp, gb, geom, rows, CS, CDy, scale=None, bias_dot=None, dot=None):
@@ -718,15 +723,11 @@ def _gtail_bwd_raw(dy, img, y, w, geom, want_w, want_bias, grid_cap=0):
     _need_cuda(dy, img, y, w)
     assert dy.shape == img.shape == (N, H, W, 8) and dy.dtype == img.dtype == y.dtype and img.is_contiguous() and y.is_contiguous()
     d, dz, dsc, _wpk = _dgrad_desc(dy, w, geom, (H, W), y.dtype, mask=y, want_sumpool=True)
-    rows = pad_to(8, 32)
-    dwp = _arena.zeros((9, rows, CS), y.device) if want_w else None
-    gb = _arena.zeros((16, 8), y.device) if want_w and want_bias else None      # XMC_BIAS_REPLICAS
+    rows, dwp, gb = _wgrad_accums(geom, CS, 8, y.device, want_bias, want_w)
     with prof.launch("gtail_bwd_kernel (conv_out dgrad + wgrad + tanh', one pass)", 2.0 * N * H * W * 8 * 32 * 9 * (2 if want_w else 1),
                      f"gtail-bwd {y.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(dy, img, y, dz, dsc)):
-        rc = L.load().xmc_gtail_bwd(C.byref(d), _p(img), _p(dwp), _p(gb), rows, int(grid_cap), _st())
-    if rc == 1:
-        return None
-    L.check(rc, "xmc_gtail_bwd")
+        if not _try_launch("xmc_gtail_bwd", C.byref(d), _p(img), _p(dwp), _p(gb), rows, int(grid_cap), _st()):
+            return None
     if not want_w:
         return dz, dsc, None, None
     r = _wgrad_unpack(dwp, gb, geom, rows, CS, 8)
@@ -806,11 +807,9 @@ def _gentry_fwd_raw(x, ps, w, bias, geom, pair=False, grid_cap=0):
     sc = torch.empty((N, H, W, geom.cout), dtype=x.dtype, device=x.device)
     with prof.launch("gentry_fwd_kernel (affine pair + 1x1 shortcut, one pass)", 2.0 * N * H * W * geom.cout * geom.cin,
                      f"gentry-fwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(x, h, sc)):
-        rc = L.load().xmc_gentry_fwd(_p(x), *[_p(t) for t in ps], _p(wpk), _p(bias), _p(h), _p(sc), N, H, W, Cc, geom.cout,
-                                     wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st())
-    if rc == 1:
-        return None
-    L.check(rc, "xmc_gentry_fwd")
+        if not _try_launch("xmc_gentry_fwd", _p(x), *[_p(t) for t in ps], _p(wpk), _p(bias), _p(h), _p(sc), N, H, W, Cc, geom.cout,
+                           wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st()):
+            return None
     return h, sc
 
 
@@ -830,11 +829,9 @@ def _gentry_bwd_raw(x, dy, dsc, ps, w, geom, want_sumpool=False, grid_cap=0):
     red = _zeros_f32((4, N, Cc), x.device)
     with prof.launch("gentry_bwd_kernel (1x1 shortcut dgrad + affine pair backward, one pass)", 2.0 * N * H * W * geom.cout * geom.cin,
                      f"gentry-bwd {x.dtype} N{N} {H}x{W} {geom.cin}->{geom.cout}", _nbytes(x, dy, dsc, dx, dxp)):
-        rc = L.load().xmc_gentry_bwd(_p(x), _p(dy), _p(dsc), *[_p(t) for t in ps], _p(wpk), _p(dx), _p(dxp), *[_p(red[i]) for i in range(4)],
-                                     N, H, W, Cc, geom.cout, wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st())
-    if rc == 1:
-        return None
-    L.check(rc, "xmc_gentry_bwd")
+        if not _try_launch("xmc_gentry_bwd", _p(x), _p(dy), _p(dsc), *[_p(t) for t in ps], _p(wpk), _p(dx), _p(dxp), *[_p(red[i]) for i in range(4)],
+                           N, H, W, Cc, geom.cout, wpk.shape[1], 0.2, _code(x.dtype), int(grid_cap), _st()):
+            return None
     return dx, red, dxp
 
 
@@ -906,7 +903,7 @@ def _dstem_fwd_raw(xin, wsets, bias, slope=0.2, want_sc=True):
     L.call("xmc_dstem_pack", _p(wsets), _p(wfrag), _st())
     h1 = torch.empty((N, H // 2, W // 2, 64), dtype=xin.dtype, device=xin.device)
     sc = torch.empty_like(h1) if want_sc else None
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + (3 * 16 if want_sc else 0)),
+    with prof.launch(_IGEMM, 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + (3 * 16 if want_sc else 0)),
                      f"dstem-fwd {xin.dtype} N{N} {H}x{W} 3->64{'+64' if want_sc else ''} k6s2", _nbytes(xin, h1, sc)):
         L.call("xmc_dstem_fwd", _p(xin), _p(wfrag), _p(bias), _p(h1), _p(sc), N, H, W, float(slope), _st())
     return h1, sc
@@ -933,7 +930,7 @@ def _dstem_dgrad_raw(dh1, dsc, wsets, D, H, W):
     dh1, dsc = dh1.contiguous(), dsc.contiguous()
     frag = torch.empty(36 * 1024, dtype=torch.uint8, device=dh1.device)
     dimg = torch.empty((N, H, W, 8), dtype=dh1.dtype, device=dh1.device)
-    with prof.launch("igemm_kernel (conv fwd+dgrad, MFMA implicit GEMM)", 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + 3 * 16),
+    with prof.launch(_IGEMM, 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + 3 * 16),
                      f"dstem-dgrad {dh1.dtype} N{N} {H}x{W} 64+64->3 k6s2", _nbytes(dh1, dsc, dimg)):
         L.call("xmc_dstem_dgrad", _p(dh1), _p(dsc), _p(wsets), _p(D), _p(frag), _p(dimg), N, H, W, _st())
     return dimg
@@ -949,7 +946,7 @@ def _dstem_wgrad_raw(xin, dh1, dsc, skip_border=False, border=True):
     flat = _arena.zeros((n_w + 128 + n_d + 64 * 8,), xin.device)
     dw, db = flat[:n_w].view(128, 36, 8), flat[n_w:n_w + 128]
     dD, dDB = flat[n_w + 128:n_w + 128 + n_d].view(64, 28, 8), flat[n_w + 128 + n_d:].view(64, 8)
-    with prof.launch("wgrad_kernel (conv weight gradient, MFMA + split-K atomics)", 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + 3 * 16),
+    with prof.launch(_WGRAD, 2.0 * N * (H // 2) * (W // 2) * 64 * (3 * 36 + 3 * 16),
                      f"dstem-wgrad {xin.dtype} N{N} {H}x{W} 3->64+64 k6s2", _nbytes(xin, dh1, dsc)):
         L.call("xmc_dstem_wgrad", _p(xin), _p(dh1), _p(dsc), _p(dw), _p(db), N, H, W, 1 if skip_border else 0, _st())
     if border:
