@@ -889,6 +889,25 @@ int64_t xmc_inception_score_ws_bytes(int N, int C, int splits);
 int xmc_inception_score(const float* logits, int64_t ld, double* H, double* P, double* ws, int64_t ws_bytes, int N, int C, int splits,
                         void* stream);
 
+/* ---- VGG-19 feature loss: the pointwise stages of the frozen network (csrc/vgg.hip; xmc_gan_amd/vgg.py) -----------------------------------
+ * Streaming kernels on NHWC tensors of dtype XMC_BF16 (this build's 16-bit format) or XMC_F32, f32 arithmetic, one writer per element, no
+ * atomics: the same inputs give the same bytes.
+ *   vgg_prep_fwd: x [N,H,W,8], the engine image in [-1, 1] (channels 3..7 are padding) -> y [N,H,W,8]:
+ *           y_c = ((x_c + 1) / 2 - mean_c) / std_c for c < 3 with torchvision's ImageNet mean (0.485, 0.456, 0.406) and std
+ *           (0.229, 0.224, 0.225); y_c = 0 for c >= 3 whatever x holds there.
+ *   vgg_prep_bwd: dx_c = dy_c * 0.5 / std_c for c < 3, 0 for c >= 3.
+ *   relu_maxpool2_fwd: z [N,H,W,C] -> p [N,H/2,W/2,C], p = max(0, max of the 2x2 window of z) = F.max_pool2d(F.relu(z), 2).
+ *   relu_maxpool2_bwd: dz [N,H,W,C] from z and dp [N,H/2,W/2,C]: the FIRST position of a window, in the row-major order (0,0) (0,1) (1,0)
+ *           (1,1), whose z equals the window's maximum gets dp when that maximum is > 0; every other position gets 0 (torch's max_pool2d
+ *           tie rule composed with ReLU's zero gradient at <= 0).  The position is recomputed from z: no index tensor is stored.  A window
+ *           that holds a NaN is outside what is specified.
+ * XMC_EINVAL: a NULL pointer, a dtype that is neither code, p == z / dz == z / dz == dp.  XMC_ESHAPE: N, H or W < 1; for the pool also
+ * C % 8 != 0, C < 8, H or W odd.  XMC_EALIGN: a pointer that is not 16-byte aligned.  All refused before any launch. */
+int xmc_vgg_prep_fwd(const void* x, void* y, int N, int H, int W, int dtype, void* stream);
+int xmc_vgg_prep_bwd(const void* dy, void* dx, int N, int H, int W, int dtype, void* stream);
+int xmc_relu_maxpool2_fwd(const void* z, void* p, int N, int H, int W, int C, int dtype, void* stream);
+int xmc_relu_maxpool2_bwd(const void* z, const void* dp, void* dz, int N, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,10 @@ _SIGS = {
     "xmc_clip_text_embed": [vp, vp, vp, vp, i32, i32, i32, i64, i32, vp],
     "xmc_clip_pool_ln": [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "xmc_clip_cosine": [vp, vp, vp, vp, i32, i32, i32, vp],
+    "xmc_vgg_prep_fwd": [vp, vp, i32, i32, i32, i32, vp],
+    "xmc_vgg_prep_bwd": [vp, vp, i32, i32, i32, i32, vp],
+    "xmc_relu_maxpool2_fwd": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "xmc_relu_maxpool2_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
 }
 _RESTYPE = {"xmc_contrastive_ws_bytes": i64, "xmc_conv_splitk_ws_bytes": i64, "xmc_attn_pool_ws_floats": i64, "xmc_last_kernel": C.c_char_p,
             "xmc_inception_score_ws_bytes": i64}

@@ -1,7 +1,8 @@
 """xmc_gan_amd.ops, layer 8 (the last): one-line functional wrappers over the nodes.  May import every other module of the package."""
 import torch
 from ._config import act_dtype
-from ._nodes_leaf import AxpbyFn, AxpbyUpFn, CastFn, DiffAugFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, SumPool2Fn, Up2Fn
+from ._nodes_leaf import (
+    AxpbyFn, AxpbyUpFn, CastFn, DiffAugFn, GapFn, LreluFn, NchwToNhwc8Fn, Nhwc8ToNchwFn, ReluMaxPool2Fn, SumPool2Fn, Up2Fn, VggPrepFn)
 from ._nodes_conv import UpConvFn
 from ._nodes_block import Affine2LreluFn, AttnPoolFn, GroupNormFn
 from ._nodes_loss import ContrastiveFn, HingeFn
@@ -81,3 +82,13 @@ def diffaug(x_nhwc8, params, cut, color=True, channels=3):
     """differentiable augmentation of [N,H,W,8] images from the device rows ``params`` f32 [N,8] = (b, s, c, tx, ty, cy, cx, 0) and the cutout
     side ``cut`` (xmc_gan_amd.augment.DiffAugment draws them); ``color=False``: no row has a colour component (one launch instead of two)"""
     return DiffAugFn.apply(x_nhwc8, params, cut, color, channels)
+
+
+def vgg_prep(x_nhwc8):
+    """the engine image [N,H,W,8] in [-1, 1] as VGG's input: ((x + 1) / 2 - mean) / std with the ImageNet statistics, padding channels zero"""
+    return VggPrepFn.apply(x_nhwc8)
+
+
+def relu_maxpool2(z):
+    """max_pool2d(relu(z), 2) of a convolution's raw output [N,H,W,C] (H, W even), forward and backward in one pass each"""
+    return ReluMaxPool2Fn.apply(z)

@@ -289,6 +289,81 @@ class Nhwc8ToNchwFn(torch.autograd.Function):
         return NchwToNhwc8Fn.apply(dy, ctx.dtype), None
 
 
+# ------------------------------------------------------------------------------------------ the frozen VGG-19's pointwise stages
+def _vgg_image(x, what):
+    _need_cuda(x)
+    if x.dim() != 4 or x.shape[-1] != 8:
+        raise ValueError(f"{what}: an engine image [N,H,W,8] expected, got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+class VggPrepFn(torch.autograd.Function):
+    """((x + 1) / 2 - mean) / std of the engine image [N,H,W,8] in [-1, 1] with torchvision's ImageNet statistics; the five padding channels
+    come out zero (xmc_gan_hip.h: xmc_vgg_prep_fwd)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _vgg_image(x, "vgg_prep")
+        y = torch.empty_like(x)
+        L.call("xmc_vgg_prep_fwd", _p(x), _p(y), *x.shape[:3], _code(x.dtype), _st())
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return VggPrepBwdFn.apply(dy)
+
+
+class VggPrepBwdFn(torch.autograd.Function):
+    """dx = dy * 0.5 / std on the three colour channels, zero on the rest; a diagonal map, so it is its own backward."""
+
+    @staticmethod
+    def forward(ctx, dy):
+        dy = _vgg_image(dy, "vgg_prep backward")
+        dx = torch.empty_like(dy)
+        L.call("xmc_vgg_prep_bwd", _p(dy), _p(dx), *dy.shape[:3], _code(dy.dtype), _st())
+        return dx
+
+    @staticmethod
+    def backward(ctx, g):
+        return VggPrepBwdFn.apply(g)
+
+
+class ReluMaxPool2Fn(torch.autograd.Function):
+    """F.max_pool2d(F.relu(z), 2) of a raw convolution output z [N,H,W,C] in one pass; the backward writes the gradient in front of the
+    convolution in one pass over (z, dp), with torch's tie rule (xmc_gan_hip.h: xmc_relu_maxpool2_bwd)."""
+
+    @staticmethod
+    def forward(ctx, z):
+        _need_cuda(z)
+        z = z.contiguous()
+        N, H, W, Cc = z.shape
+        p = torch.empty((N, H // 2, W // 2, Cc), dtype=z.dtype, device=z.device)
+        L.call("xmc_relu_maxpool2_fwd", _p(z), _p(p), N, H, W, Cc, _code(z.dtype), _st())
+        ctx.save_for_backward(z)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        (z,) = ctx.saved_tensors
+        return ReluMaxPool2BwdFn.apply(z, dp)
+
+
+class ReluMaxPool2BwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, dp):
+        dp = dp.contiguous()
+        if dp.dtype != z.dtype:
+            dp = dp.to(z.dtype)
+        N, H, W, Cc = z.shape
+        dz = torch.empty_like(z)
+        L.call("xmc_relu_maxpool2_bwd", _p(z), _p(dp), _p(dz), N, H, W, Cc, _code(z.dtype), _st())
+        return dz
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError("second derivative through relu_maxpool2 is not on the XMC-GAN path")
+
+
 # ------------------------------------------------------------------------------------------ differentiable augmentation
 def _diffaug_raw(x, params, cut, color, channels, transposed, linear_only):
     """one sums launch (only with a colour component) and one apply launch of csrc/augment.hip"""

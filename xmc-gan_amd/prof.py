@@ -1,5 +1,7 @@
 """Per-launch timing of the convolution kernels with HIP events recorded on the launch stream
 (bench.py's `roofline` object).  Disabled by default: zero overhead on the normal path."""
+import collections
+
 import torch
 
 _on = False
@@ -41,6 +43,15 @@ class launch:
             from . import lib
             kern = lib.load().xmc_last_kernel().decode()       # the instantiation the C dispatcher picked
             _recs.append((self.family, self.flops, self.e0, self.e1, self.tag, kern, self.nbytes))
+
+
+Launch = collections.namedtuple("Launch", "family tag kernel flops nbytes ms")
+
+
+def launches():
+    """the recorded launches in order, each with its device time (synchronises): what a per-launch table or a launch-list comparison reads"""
+    torch.cuda.synchronize()
+    return [Launch(family, tag, kern, flops, nb, e0.elapsed_time(e1)) for family, flops, e0, e1, tag, kern, nb in _recs]
 
 
 def _aggregate_where(pred):

@@ -44,6 +44,7 @@ from xmc_gan_amd.augment import DiffAugment, parse_policy
 from xmc_gan_amd.evaluate import MetricSuite, resolve_weights
 from xmc_gan_amd.graph import CaptureFailed, GraphedIteration
 from xmc_gan_amd.optim import HipAdam, ParamEMA
+from xmc_gan_amd.vgg import VGG19Features, VGGContrast, resolve_vgg_weights
 
 _GEN_ARCH = {"DF_GEN": DF_GEN, "CONCEPT_IN_DF_GEN": CONCEPT_IN_DF_GEN, "CONCEPT_OUT_DF_GEN": CONCEPT_OUT_DF_GEN,
              # word-attention generators of model/concept_gan.py; upstream keeps these two names commented out (train_gan.py:44)
@@ -110,6 +111,11 @@ def parse_args(argv=None):
     parser.add_argument('--diffaug', type=str, default='',
                         help="differentiable augmentation of every image the discriminator sees: comma list out of color, translation, "
                              "cutout (typical: all three).  '' (default): off")
+    parser.add_argument('--vgg_weights', type=str, default='', metavar='PATH',
+                        help="TRAIN.ENCODER_LOSS.VGG: torchvision's VGG-19 weights (the vgg19-dcbb9e9d.pth state dict) of the frozen network "
+                             "behind the image-image contrastive term (default: $XMC_VGG19).  Without the switch nothing is loaded")
+    parser.add_argument('--vgg_smooth', type=float, default=1.0, metavar='FLOAT',
+                        help="weight of the VGG term in the generator's loss (the reference's yml schema has no SMOOTH.VGG; default 1.0)")
     parser.add_argument('--image_cache', type=str, default='', metavar='DIR',
                         help='train and evaluate from the uint8 image cache in DIR (built by xmc_gan/image_cache.py): the resized images '
                              'stay in device memory and a batch is one crop + flip + normalise launch instead of the PIL DataLoader')
@@ -170,8 +176,10 @@ def img_loss(real_imgs, fake_imgs, labels, b_global):
 class StepOptions:
     """Engine-side switches of an iteration (not part of the reference cfg)."""
 
-    def __init__(self, gather_negatives=False, graph=False, log_each_step=True, ema=None, diffaug=None):
+    def __init__(self, gather_negatives=False, graph=False, log_each_step=True, ema=None, diffaug=None, vgg=None, vgg_smooth=1.0):
         self.gather_negatives = gather_negatives
+        self.vgg = vgg                        # xmc_gan_amd.vgg.VGGContrast: the frozen network of TRAIN.ENCODER_LOSS.VGG (None without the switch)
+        self.vgg_smooth = vgg_smooth          # weight of the VGG term (--vgg_smooth; the reference's SMOOTH has no VGG entry)
         self.diffaug = diffaug                # xmc_gan_amd.augment.DiffAugment: netD sees augmented images only; train() refreshes its rows
         self.ema = ema                        # xmc_gan_amd.optim.ParamEMA of the generator: one update per applied generator step
         self.graph = graph                    # train(): replay the iteration as hipGraphs (xmc_gan_amd.graph.GraphedIteration)
@@ -415,13 +423,20 @@ def _g_step(it):
         outputs = netD.COND_DNET(features, sent_embs=it.psent_embs)
         errG_fake = -outputs[0].float().mean()
         enc_loss = 0.0
-        real_pooled = fake_pooled = None
+        real_pooled = fake_pooled = real_vgg = fake_vgg = None
+        if E.VGG:
+            if it.opts.vgg is None:
+                raise ImportError('TRAIN.ENCODER_LOSS.VGG is on and the iteration was handed no VGG-19: --vgg_weights PATH (StepOptions(vgg=))')
+            # the plain images, not the augmented ones: the augmentation is there for the discriminator's overfitting, and VGG is not it
+            real_vgg, fake_vgg = it.opts.vgg.rows(it.imgs_h if it.imgs_h is not None else ops.to_nhwc8(it.imgs),
+                                                  it.fake_h if it.fake_h is not None else ops.to_nhwc8(it.fake))
         if E.DISC:
             with torch.no_grad():            # (augmented: the same rows as the generated images it is compared with)
                 real_pooled = ops.global_avgpool(see(it.imgs, it.imgs_h, see.rows('g')).permute(0, 2, 3, 1).contiguous())
             fake_pooled = ops.global_avgpool(features.permute(0, 2, 3, 1).contiguous())
         # what the contrastive terms of this step compare across ranks, all-gathered in ONE collective (a seam of the captured iteration each)
-        rows = it.gather_all(([outputs[1], outputs[2]] if E.SENT else []) + ([real_pooled, fake_pooled] if E.DISC else []))
+        rows = it.gather_all(([outputs[1], outputs[2]] if E.SENT else []) + ([real_pooled, fake_pooled] if E.DISC else [])
+                             + ([real_vgg, fake_vgg] if E.VGG else []))
         if E.SENT:
             gs_loss = sent_loss(imgs=rows[0], txts=rows[1], labels=it.labels, b_global=E.B_GLOBAL)
             enc_loss = enc_loss + T.SMOOTH.SENT * gs_loss
@@ -429,11 +444,14 @@ def _g_step(it):
         if E.WORD:
             raise NotImplementedError
         if E.DISC:
-            disc_loss = img_loss(real_imgs=rows[-2], fake_imgs=rows[-1], labels=it.labels, b_global=E.B_GLOBAL)
+            d0 = 2 if E.SENT else 0
+            disc_loss = img_loss(real_imgs=rows[d0], fake_imgs=rows[d0 + 1], labels=it.labels, b_global=E.B_GLOBAL)
             enc_loss = enc_loss + T.SMOOTH.DISC * disc_loss
             out['disc_loss'] = disc_loss.detach()
         if E.VGG:
-            raise NotImplementedError
+            vgg_loss = img_loss(real_imgs=rows[-2], fake_imgs=rows[-1], labels=it.labels, b_global=E.B_GLOBAL)
+            enc_loss = enc_loss + it.opts.vgg_smooth * vgg_loss
+            out['vgg_loss'] = vgg_loss.detach()
         errG = errG_fake + enc_loss
         it.netG.zero_grad()
         netD.zero_grad()
@@ -509,7 +527,8 @@ def _log_epoch_scalars(writer, last, epoch):
         return
     writer.add_scalar('epoch', epoch, epoch)
     for tag, key in (('Loss_D', 'errD'), ('Loss_G', 'errG'), ('errD_real', 'errD_real'), ('errD_fake', 'errD_fake'),
-                     ('errD_mismatch', 'errD_mismatch'), ('ds_loss', 'ds_loss'), ('gs_loss', 'gs_loss'), ('disc_loss', 'disc_loss')):
+                     ('errD_mismatch', 'errD_mismatch'), ('ds_loss', 'ds_loss'), ('gs_loss', 'gs_loss'), ('disc_loss', 'disc_loss'),
+                     ('vgg_loss', 'vgg_loss')):
         if key in last:
             writer.add_scalar(tag, last[key].item(), epoch)
     writer.flush()
@@ -1025,6 +1044,10 @@ def _checked_args(argv):
         cfg.TRAIN.MAX_EPOCH = args.max_epoch
     if args.precision:
         ops.set_precision(args.precision)
+    # the VGG term's weights: refused here, at start-up, and not at the first generator step.  Without the switch nothing is looked for
+    args.vgg_weights = resolve_vgg_weights(args.vgg_weights) if cfg.TRAIN.ENCODER_LOSS.VGG else ''
+    if cfg.TRAIN.ENCODER_LOSS.VGG and cfg.IMG.SIZE % 32:
+        raise SystemExit(f'TRAIN.ENCODER_LOSS.VGG: five 2x2 pools need an image size that is a multiple of 32, got {cfg.IMG.SIZE}')
     fid_inception = resolve_weights(args.fid_inception, 'XMC_FID_INCEPTION', '--fid_inception', must_exist=False)
     if not 0 <= args.prdc <= 16:
         raise SystemExit('--prdc K: 0 (off) or 1 <= K <= 16 nearest neighbours')
@@ -1118,11 +1141,18 @@ def main(argv=None):
             aug.seed(args.seed, rank, state_epoch)
         logger.info(f'DiffAugment on the discriminator inputs: {",".join(aug.policy)}')
 
+    # the frozen VGG-19 of TRAIN.ENCODER_LOSS.VGG: held by the step options, not by netG / netD (nothing of it reaches a checkpoint); its
+    # packed weights are made here, before any capture
+    vgg = None
+    if cfg.TRAIN.ENCODER_LOSS.VGG:
+        vgg = VGGContrast(VGG19Features(args.vgg_weights, device).warm())
+        logger.info(f'VGG-19 image-image contrastive term: weights {args.vgg_weights}, weight {args.vgg_smooth}')
+
     writer = ScalarLog(log_dir, args.log_type, run_name=cfg.CONFIG_NAME) if rank == 0 else None
     last = train(train_loader=train_loader, test_loader=test_loader, state_epoch=state_epoch, text_encoder=text_encoder,
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
                  opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
-                                  ema=ema, diffaug=aug),
+                                  ema=ema, diffaug=aug, vgg=vgg, vgg_smooth=args.vgg_smooth),
                  img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts, clip_dir=args.clip_dir or None)
     if writer is not None:
         writer.close()
