@@ -66,6 +66,8 @@ extern "C" {
  *     XmcOptimStep + xmc_optim_step replace xmc_adam_step, xmc_adam_step_scaled, xmc_adam_ema_step and xmc_adam_ema_step_scaled.
  *     Added under 13 (additions only): xmc_clip_resize_h_u8 / xmc_clip_resize_v_u8 / xmc_attention_causal / xmc_bias_quick_gelu /
  *     xmc_clip_vision_embed / xmc_clip_text_embed / xmc_clip_pool_ln / xmc_clip_cosine (csrc/clip.hip). */
+/* Long sequences, also an addition under 13: xmc_attention_long (csrc/attention_long.hip) -- f32 attention for 1 <= T <= 1024 on the
+ * exact-f32 MFMA, K and V streamed through LDS in 64-key tiles, key padding (`lens`, nullable) and the causal mask together. */
 #define XMC_ABI_VERSION 13
 
 /* XMC_BF16 names the 16-bit storage / MFMA-operand format THIS BUILD of the library was compiled for: bf16 in
@@ -408,6 +410,9 @@ int xmc_clip_resize_h_u8(const uint8_t* src, uint8_t* dst, const int32_t* bounds
 int xmc_clip_resize_v_u8(const uint8_t* src, void* dst, const int32_t* bounds, const int32_t* coeffs, const float* lut, int N, int H, int W,
                          int OH, int ksize, int mode, int S, int P, int top, int left, void* stream);
 int xmc_attention_causal(const float* qkv, float* out, int B, int T, int heads, int head_dim, void* stream);
+/* qkv f32 [B*T, 3H] rows [Q | K | V] (H = heads * 64, 16-byte aligned), out f32 [B*T, H]; query r of sample b sees keys j < len_b =
+ * clamp(lens[b], 0, T) (T when lens is NULL) and, if `causal`, j <= r; rows r >= len_b come back as zeros.  1 <= T <= 1024, head_dim 64. */
+int xmc_attention_long(const float* qkv, const int32_t* lens, float* out, int B, int T, int heads, int head_dim, int causal, void* stream);
 int xmc_bias_quick_gelu(const float* x, const float* bias, float* out, int64_t rows, int F, void* stream);
 int xmc_clip_vision_embed(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta, float* out, int N,
                           int GG, int H, float eps, void* stream);

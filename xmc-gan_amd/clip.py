@@ -7,9 +7,15 @@ there, ``preprocessor_config.json`` -- no third-party model code -- and runs bot
 integer bicubic resize with the crop, the normalisation and the patch order in its second pass; the two embedding blocks; causal
 attention; QuickGELU; the pooled-row LayerNorm; the cosine).  No atomics: the same inputs give the same bytes.
 
-The text tower's context is ``min(max_position_embeddings, 64)`` tokens, the longest sequence the attention kernels take.  Attention is
-causal and the pooled row is the caption's EOS, so nothing after the EOS reaches a feature: a caption of at most 62 BPE tokens gets the
-feature it gets at CLIP's own context of 77; a longer one is truncated earlier than upstream would (counted in ``n_truncated``).
+By default the text tower's context is ``min(max_position_embeddings, 64)`` tokens, the longest sequence the short attention kernels take.
+Attention is causal and the pooled row is the caption's EOS, so nothing after the EOS reaches a feature: a caption of at most 62 BPE tokens
+gets the feature it gets at CLIP's own context of 77; a longer one is truncated earlier than upstream would (counted in ``n_truncated``).
+
+``CLIPScorer(model_dir, device, max_tokens=N)`` with N in (64, 1024] opts into ``ops.attention_long`` (csrc/attention_long.hip: f32 MFMA
+attention with K and V streamed through LDS): a vision tower of up to N tokens is accepted (ViT-B/16 has 197, L/14 257, L/14 at 336 px
+577) and the context is ``min(max_position_embeddings, N)``, CLIP's own 77, so that truncation and ``n_truncated`` follow upstream.  Each
+tower keeps ONE attention kernel, chosen at construction by its longest sequence (``tokens`` / ``context``): at most 64 the short kernels,
+beyond that ``attention_long`` for every call, so a caption's bytes never depend on the longest caption of its batch.
 """
 import json
 import os
@@ -54,7 +60,10 @@ class CLIPScorer:
     """``encode_images`` / ``tokenize`` / ``encode_text_ids`` / ``encode_text`` / ``score``; ``n_truncated`` counts the captions
     ``tokenize`` cut to the context."""
 
-    def __init__(self, model_dir, device=None):
+    def __init__(self, model_dir, device=None, max_tokens=MAX_CONTEXT):
+        if isinstance(max_tokens, bool) or not isinstance(max_tokens, int) or not MAX_CONTEXT <= max_tokens <= ops.ATTENTION_LONG_MAX_T:
+            raise ValueError(f"CLIPScorer: max_tokens must be an integer in [{MAX_CONTEXT}, {ops.ATTENTION_LONG_MAX_T}], got {max_tokens!r}")
+        self.max_tokens = max_tokens
         if not model_dir or not os.path.isdir(model_dir):
             raise ImportError(f"CLIPScorer needs a Hugging Face CLIPModel directory ({_FILES}; e.g. a copy of openai/clip-vit-base-patch32); "
                               f"{model_dir!r} is not a directory")
@@ -82,12 +91,18 @@ class CLIPScorer:
             raise ValueError(f"CLIPScorer: image_size {self.image_size} is no multiple of patch_size {self.patch}")
         self.grid = self.image_size // self.patch
         self.tokens = self.grid * self.grid + 1
-        if self.tokens > MAX_CONTEXT:
+        if self.tokens > max_tokens and max_tokens > MAX_CONTEXT:
+            raise NotImplementedError(f"CLIPScorer: image_size {self.image_size} / patch_size {self.patch} gives {self.tokens} tokens, more than "
+                                      f"max_tokens={max_tokens} (--clip_max_tokens) admits; {self.tokens} or more, up to "
+                                      f"{ops.ATTENTION_LONG_MAX_T}, takes this model")
+        if self.tokens > MAX_CONTEXT and max_tokens == MAX_CONTEXT:
             raise NotImplementedError(f"CLIPScorer: the attention kernel takes at most {MAX_CONTEXT} tokens; image_size {self.image_size} / "
                                       f"patch_size {self.patch} gives {self.tokens} (ViT-B/32 at 224 has 50; B/16 and L/14 are not built)")
         self.bos_id, self.eos_id = int(tc.get("bos_token_id", 49406)), int(tc.get("eos_token_id", 49407))
         self.pad_id = int(tc["pad_token_id"]) if tc.get("pad_token_id") is not None else 0
-        self.context = min(self.npos, MAX_CONTEXT)
+        self.context = min(self.npos, max_tokens)
+        # one attention kernel per tower, by its longest sequence: a sample's bytes do not depend on its batch
+        self.vision.long, self.text.long = self.tokens > MAX_CONTEXT, self.context > MAX_CONTEXT
         self.n_truncated = 0
         self.image_batch = 256
         self._tokenizer = None
@@ -181,12 +196,15 @@ class CLIPScorer:
         """the pre-LayerNorm transformer layers of one tower over the residual stream x f32 [B*T, W]"""
         w = self._w
         g_qkv, g_o, g_up, g_down = tw.geoms
-        full = None if causal else torch.full((B,), T, dtype=torch.int32, device=x.device)
+        full = None if causal or tw.long else torch.full((B,), T, dtype=torch.int32, device=x.device)
         for i in range(tw.layers):
             g = lambda n: w[f"{pre}.{i}.{n}"]      # noqa: E731
             h, _ = ops.add_layernorm(x, None, g("ln1g"), g("ln1b"), tw.eps)
             qkv = self._gemm(h, g("wqkv"), g("bqkv"), g_qkv)
-            ctx = ops.attention_causal(qkv, B, T, tw.heads) if causal else ops.attention_short(qkv, full, B, T, tw.heads)
+            if tw.long:
+                ctx = ops.attention_long(qkv, None, B, T, tw.heads, causal=causal)
+            else:
+                ctx = ops.attention_causal(qkv, B, T, tw.heads) if causal else ops.attention_short(qkv, full, B, T, tw.heads)
             x = self._gemm(ctx, g("wo"), g("bo"), g_o, res=x)
             h, _ = ops.add_layernorm(x, None, g("ln2g"), g("ln2b"), tw.eps)
             up = self._gemm(h, g("w1"), None, g_up)

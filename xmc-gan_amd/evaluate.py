@@ -31,12 +31,15 @@ def image_set_kind(path):
     return "dir" if os.path.isdir(path) else "npz" if os.path.isfile(path) and path.endswith(".npz") else None
 
 
-def load_model(kind, path, device):
+def load_model(kind, path, device, max_tokens=64):
     """the Inception extractor ('inception') or DAMSM image encoder ('damsm') of a weights file, or the CLIP scorer ('clip') of a model
-    directory: one per kind, reloaded when the file (the directory's config.json), its modification time or the device is another"""
+    directory: one per kind, reloaded when the file (the directory's config.json), its modification time, the device or ``max_tokens``
+    (`CLIPScorer`'s longest sequence; read for 'clip' only) is another"""
     import torch
     stamp = os.path.join(path, "config.json") if kind == "clip" else path
     key = (os.path.abspath(path), os.stat(stamp).st_mtime_ns if os.path.isfile(stamp) else None, str(torch.device(device)))
+    if kind == "clip":
+        key += (int(max_tokens),)
     if _models.get(kind, (None, None))[0] != key:
         _models.pop(kind, None)
         if kind == "inception":
@@ -44,7 +47,7 @@ def load_model(kind, path, device):
             _models[kind] = key, F.InceptionFID(path, device)
         elif kind == "clip":
             from . import clip as CL
-            _models[kind] = key, CL.CLIPScorer(path, device)
+            _models[kind] = key, CL.CLIPScorer(path, device, int(max_tokens))
         else:
             from . import rprecision as RP
             _models[kind] = key, RP.load_image_encoder(path, None, device)
@@ -61,10 +64,10 @@ class MetricSuite:
     ``kid``: the Kernel Inception Distance over ``kid_subsets`` subsets of ``kid_subset_size`` rows; it is two-sided, takes the feature rows
     and shares PRDC's bank and cache file: with both on, the rows are stored, read and written once.  ``inception_score`` > 0: the Inception
     Score over that many splits, one-sided like R-precision.  ``clip_dir``: CLIPScore with the CLIP model directory there, one-sided, from the
-    caption strings ``update_fake`` is given."""
+    caption strings ``update_fake`` is given; ``clip_max_tokens`` is `CLIPScorer`'s ``max_tokens`` (64: ViT-B/32 at a text context of 64)."""
 
     def __init__(self, device, fid_inception="", prdc_k=0, damsm_image_encoder="", text_encoder=None, rp_k=100, rp_splits=10, rp_seed=0, fid=True,
-                 kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0, inception_score=0, clip_dir=""):
+                 kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0, inception_score=0, clip_dir="", clip_max_tokens=64):
         self.device, self.prdc_k, self.why = device, int(prdc_k), {}
         self.kid_args, is_splits = (int(kid_subsets), int(kid_subset_size), int(kid_seed)), int(inception_score)
         self.extractor = self.encoder = self._cache_dir = None
@@ -101,7 +104,8 @@ class MetricSuite:
                 self.why[RPREC] = why
         if clip_dir:
             from .clip import CLIPScoreStats
-            self.fake[CLIP] = CLIPScoreStats(load_model("clip", clip_dir, device))
+            more = {} if int(clip_max_tokens) == 64 else {"max_tokens": int(clip_max_tokens)}      # off: the call it was
+            self.fake[CLIP] = CLIPScoreStats(load_model("clip", clip_dir, device, **more))
         self._rows = PRDC if PRDC in self.fake else KID                # the metric the bank of rows and its real side are kept under
         self._two_sided = [m for m in (FID, self._rows) if m in self.fake]
 

@@ -191,6 +191,7 @@ _SIGS = {
     "xmc_clip_resize_h_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_clip_resize_v_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "xmc_attention_causal": [vp, vp, i32, i32, i32, i32, vp],
+    "xmc_attention_long": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "xmc_bias_quick_gelu": [vp, vp, vp, i64, i32, vp],
     "xmc_clip_vision_embed": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "xmc_clip_text_embed": [vp, vp, vp, vp, i32, i32, i32, i64, i32, vp],

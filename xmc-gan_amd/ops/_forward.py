@@ -679,6 +679,26 @@ def attention_causal(qkv, B, T, heads):
     return _attention("attention_causal", qkv, None, B, T, heads, torch.float32)
 
 
+ATTENTION_LONG_MAX_T = 1024     # longest sequence of `attention_long` (AL_MAX_T of csrc/attention_long.hip)
+
+
+def attention_long(qkv, lens, B, T, heads, causal=False):
+    """softmax(Q K^T / sqrt(64) + mask) V for 1 <= T <= 1024 on the exact-f32 MFMA, K and V streamed through LDS in 64-key tiles with a
+    running maximum and sum (csrc/attention_long.hip): qkv f32 [B*T,3H] as `attention_short` takes it; query r of sample b sees keys
+    j < lens[b] (int32 [B]; T when ``lens`` is None) and, with ``causal``, j <= r.  Rows of padded queries come back as zeros.
+    A sample's bytes depend neither on T nor on the batch nor on what lies behind its length.  Returns f32 [B*T,H]."""
+    if not qkv.is_cuda:
+        raise RuntimeError("xmc_gan_amd.ops.attention_long: CPU tensors are not supported (no CPU fallback)")
+    _enc_f32c(qkv)
+    assert qkv.dim() == 2 and qkv.shape[0] == B * T and qkv.shape[1] % (3 * heads) == 0
+    d = qkv.shape[1] // (3 * heads)
+    assert d == 64 and 1 <= T <= ATTENTION_LONG_MAX_T, f"attention_long is built for head dimension 64 and T <= 1024, got d={d}, T={T}"
+    assert lens is None or (lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == B and lens.is_cuda)
+    out = torch.empty(B * T, heads * d, dtype=torch.float32, device=qkv.device)
+    L.call("xmc_attention_long", _p(qkv), _p(lens), _p(out), B, T, heads, d, int(bool(causal)), _st())
+    return out
+
+
 def bias_quick_gelu(x, bias):
     """v * sigmoid(1.702 v), v = x + bias -- Hugging Face's hidden_act "quick_gelu" -- over f32 [rows,F], F % 8 == 0."""
     return _bias_act("bias_quick_gelu", x, bias, torch.float32)

@@ -1,10 +1,12 @@
 """CLIPScore of a directory of generated images against their captions, on the HIP kernels of ``xmc_gan_amd.clip``.
 
-    python xmc_gan/clip_score.py IMAGES_DIR --captions FILE --clip_dir PATH [--per_caption K] [--batch 100] [--gpu 0]
+    python xmc_gan/clip_score.py IMAGES_DIR --captions FILE --clip_dir PATH [--clip_max_tokens N] [--per_caption K] [--batch 100]
+                                 [--gpu 0]
 
 The PNG / JPEG files of ``IMAGES_DIR`` are taken in sorted order; caption ``i`` (line ``i`` of ``--captions``, blank lines skipped) belongs
 to files ``i*K .. i*K+K-1`` (the order of ``sample.py``'s file names ``<caption:05d>_<k>.png``).  ``--clip_dir`` is a Hugging Face CLIPModel
-directory, e.g. a copy of openai/clip-vit-base-patch32 (default: $XMC_CLIP_DIR).  Prints the result as one JSON object: ``clip_score`` is
+directory, e.g. a copy of openai/clip-vit-base-patch32 (default: $XMC_CLIP_DIR); ``--clip_max_tokens 77`` or more scores at CLIP's own
+text context and admits ViT-B/16 and ViT-L/14.  Prints the result as one JSON object: ``clip_score`` is
 the mean of max(100 cos, 0) over the images (Hessel et al.'s 2.5 max(cos, 0) is 0.025 times it).  INTEGRATION.md section 3.11 has the details.
 """
 import os
@@ -23,6 +25,8 @@ def parse_args(argv=None):
     parser.add_argument('images', metavar='IMAGES_DIR', help='directory of PNG / JPEG images, K consecutive files (sorted) per caption')
     parser.add_argument('--captions', type=str, required=True, metavar='FILE', help='one sentence per line')
     parser.add_argument('--clip_dir', type=str, default='', metavar='PATH', help='CLIPModel directory (default: $XMC_CLIP_DIR)')
+    parser.add_argument('--clip_max_tokens', type=int, default=64, metavar='N',
+                        help="the longest sequence CLIPScore's towers take (default 64: ViT-B/32 at a text context of 64, today's scores).  77 or more gives CLIP's own text context of 77 tokens and admits ViT-B/16 (197 tokens) and ViT-L/14 (257; 577 at 336 px); at most 1024")
     parser.add_argument('--per_caption', type=int, default=1, metavar='K')
     parser.add_argument('--batch', type=int, default=100)
     parser.add_argument('--gpu', dest='gpu_id', type=int, default=0)
@@ -64,7 +68,8 @@ def main(argv=None):
     torch.cuda.set_device(args.gpu_id)
     device = torch.device('cuda', args.gpu_id)
     try:
-        stats = CLIPScoreStats(load_model('clip', args.clip_dir, device))
+        stats = CLIPScoreStats(load_model('clip', args.clip_dir, device,
+                                          **({} if args.clip_max_tokens == 64 else {'max_tokens': args.clip_max_tokens})))
     except (ImportError, ValueError, NotImplementedError) as e:
         raise SystemExit(f'--clip_dir: {e}')
     K = args.per_caption

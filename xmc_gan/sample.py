@@ -4,7 +4,7 @@
                              (--captions FILE | --token_ids FILE.npy | --synthetic N) [--n_per_caption K --seed S --truncation PSI]
                              [--best_of M --netD netD_*.pth] [--walk N] [--interp_sent N] [--grid_max N] [--no_png]
                              [--fid_against DIR_OR_NPZ --fid_inception PATH] [--prdc_against DIR_OR_FEATURES_NPZ [--prdc_k K]]
-                             [--rprecision --damsm_image_encoder PATH] [--clip_score --clip_dir PATH]
+                             [--rprecision --damsm_image_encoder PATH] [--clip_score --clip_dir PATH [--clip_max_tokens N]]
                              [--kid_against DIR_OR_FEATURES_NPZ [--kid_subsets S --kid_subset_size M]] [--inception_score [--is_splits S]]
 
 Writes ``<out>/<caption index:05d>_<k>.png`` (K images per caption), ``<out>/grid.png`` (the first ``--grid_max`` of them, every image min-max scaled
@@ -85,6 +85,8 @@ def parse_args(argv=None):
                         help='score the sampled images: CLIPScore against the sentences of --captions -> manifest "clip_score"')
     parser.add_argument('--clip_dir', type=str, default='', metavar='PATH',
                         help='--clip_score: a Hugging Face CLIPModel directory, e.g. a copy of openai/clip-vit-base-patch32 (default: $XMC_CLIP_DIR)')
+    parser.add_argument('--clip_max_tokens', type=int, default=64, metavar='N',
+                        help="--clip_score: the longest sequence CLIPScore's towers take (default 64: ViT-B/32 at a text context of 64, today's scores).  77 or more gives CLIP's own text context of 77 tokens and admits ViT-B/16 (197 tokens) and ViT-L/14 (257; 577 at 336 px); at most 1024")
     parser.add_argument('--rp_k', type=int, default=100, metavar='K', help='--rprecision: candidates per image, the own caption included')
     parser.add_argument('--rp_splits', type=int, default=10, metavar='S', help='--rprecision: parts the mean and its spread are taken over')
     # reranking
@@ -285,9 +287,10 @@ def main(argv=None):
     if args.inception_score:
         more.update(inception_score=args.is_splits)
     if args.clip_score:
-        more.update(clip_dir=args.clip_dir)
+        tokens = {} if args.clip_max_tokens == 64 else {'max_tokens': args.clip_max_tokens}
+        more.update(clip_dir=args.clip_dir, **{'clip_' + k: v for k, v in tokens.items()})
         try:
-            load_model('clip', args.clip_dir, device)
+            load_model('clip', args.clip_dir, device, **tokens)
         except (ImportError, ValueError, NotImplementedError) as e:
             raise SystemExit(f'--clip_dir: {e}')
     suite = MetricSuite(device, args.fid_inception if (args.fid_against or args.prdc_against or args.kid_against or args.inception_score) else '', args.prdc_k if args.prdc_against else 0,

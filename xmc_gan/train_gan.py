@@ -105,6 +105,8 @@ def parse_args(argv=None):
                         help='a Hugging Face CLIPModel directory (config.json, weights, tokenizer.json; e.g. a copy of '
                              'openai/clip-vit-base-patch32): eval() also reports CLIPScore of the generated images against their captions '
                              '(default: $XMC_CLIP_DIR; without either, no CLIPScore)')
+    parser.add_argument('--clip_max_tokens', type=int, default=64, metavar='N',
+                        help="--clip_dir: the longest sequence CLIPScore's towers take (default 64: ViT-B/32 at a text context of 64, today's scores).  77 or more gives CLIP's own text context of 77 tokens and admits ViT-B/16 (197 tokens) and ViT-L/14 (257; 577 at 336 px); at most 1024")
     parser.add_argument('--sbert_dir', type=str, default='', metavar='PATH',
                         help='TEXT.ENCODER_NAME SBERT: the RoBERTa model directory of the sentence encoder (config.json, weights, tokenizer '
                              'files; default: $XMC_SBERT_DIR).  Without it the SBERT presets run with --synthetic only')
@@ -705,7 +707,7 @@ def load_average(model_dir, epoch, ema, device, logger):
 
 
 def _end_of_epoch(epoch, last, *, netG, netD, optimizerG, optimizerD, ema, netG_ema, fixed, img_dir, model_dir, test_loader, text_encoder,
-                  logger, writer, eval_opts, clip_dir=None):
+                  logger, writer, eval_opts, clip_dir=None, clip_max_tokens=64):
     """what the reference does after an epoch's last batch (train_gan.py:300-336): scalars, the sample grid from the fixed batch, and past
     epoch 50 the checkpoint and `eval`; with ``ema`` the grid, the checkpoint and `eval` take the averaged generator"""
     if parallel.rank() == 0:
@@ -732,11 +734,11 @@ def _end_of_epoch(epoch, last, *, netG, netD, optimizerG, optimizerD, ema, netG_
             # (--caption_cache: the test split's rows are another table; the train split's encoder carries the test split's)
             eval(loader=test_loader, state_epoch=epoch, text_encoder=getattr(text_encoder, 'eval_encoder', None) or text_encoder, netG=gen,
                  logger=logger, num_samples=6000, save_dir=f'{img_dir}/test' if img_dir else None, org_dir=f'{img_dir}/org' if img_dir else None,
-                 writer=writer, eval_opts=eval_opts, clip_dir=clip_dir)
+                 writer=writer, eval_opts=eval_opts, clip_dir=clip_dir, **_clip_tokens_arg(clip_max_tokens))
 
 
 def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, optimizerG, optimizerD, logger, model_dir,
-          opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None, clip_dir=None):
+          opts=None, img_dir=None, max_steps=None, writer=None, eval_opts=None, clip_dir=None, clip_max_tokens=64):
     """Epoch loop with the reference's signature (train_gan.py:142); returns the last iteration's losses.
 
     With ``img_dir`` (rank 0) it keeps the reference's visual log: ``sents.txt`` and ``imgs.png`` of the first batch (146-160),
@@ -753,7 +755,8 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
     add ``netG_ema_<epoch>.pth`` (a plain generator state dict) and ``ema_state.pth``.  ``netG`` itself keeps training.
 
     ``opts.diffaug`` (a `DiffAugment`, ``--diffaug``): its rows are redrawn before every iteration, graphed or eager.
-    ``eval_opts`` (an `EvalOptions`) and ``clip_dir`` (CLIPScore's model directory): what `eval` scores after an epoch, handed on to it."""
+    ``eval_opts`` (an `EvalOptions`) and ``clip_dir`` (CLIPScore's model directory): what `eval` scores after an epoch, handed on to it,
+    as is ``clip_max_tokens`` (`CLIPScorer`'s ``max_tokens``)."""
     device = next(netG.parameters()).device
     opts = opts or StepOptions()
     ema = opts.ema
@@ -806,7 +809,7 @@ def train(train_loader, test_loader, state_epoch, text_encoder, netG, netD, opti
         clock.after_epoch(nsteps, runner.hipgraph)
         _end_of_epoch(epoch, last, netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, ema=ema, netG_ema=netG_ema,
                       fixed=fixed, img_dir=img_dir, model_dir=model_dir, test_loader=test_loader, text_encoder=text_encoder,
-                      logger=logger, writer=writer, eval_opts=eval_opts, clip_dir=clip_dir)
+                      logger=logger, writer=writer, eval_opts=eval_opts, clip_dir=clip_dir, clip_max_tokens=clip_max_tokens)
     return finish()
 
 
@@ -865,17 +868,23 @@ def _new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score):
     return kw
 
 
+def _clip_tokens_arg(clip_max_tokens):
+    """``clip_max_tokens`` as a keyword, and no argument at all at the default of 64"""
+    return {} if int(clip_max_tokens) == 64 else {'clip_max_tokens': int(clip_max_tokens)}
+
+
 @torch.no_grad()
 def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save_dir=None, org_dir=None, writer=None, fid_inception=None,
          damsm_image_encoder=None, metrics=None, prdc=None, eval_opts=None, kid=None, kid_subsets=None, kid_subset_size=None,
-         inception_score=None, clip_dir=None):
+         inception_score=None, clip_dir=None, clip_max_tokens=64):
     """Generate images for the test loader and score them (train_gan.py:338-395): every generated image goes to ``save_dir/<key>.png`` and,
     unless ``org_dir`` already holds ``num_samples`` files, every real one to ``org_dir/<key>.png``, as 8-bit PNGs of (x + 1) * 127.5.  The
     scores are a `MetricSuite`'s (xmc_gan_amd/evaluate.py): FID with ``fid_inception`` (without it: between the two directories, when
     ``pytorch_fid`` imports), precision / recall / density / coverage with ``prdc`` = K > 0 beside it, R-precision with ``damsm_image_encoder``
     and an ``RNN_ENCODER``, the Kernel Inception Distance with ``kid`` (over ``kid_subsets`` subsets of ``kid_subset_size`` rows) and the
     Inception Score with ``inception_score`` = SPLITS > 0, both from the same Inception features; each is the keyword, else ``eval_opts``,
-    else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER; CLIPScore with ``clip_dir`` (a CLIP model directory), from the caption strings of the
+    else $XMC_FID_INCEPTION / $XMC_DAMSM_IMAGE_ENCODER; CLIPScore with ``clip_dir`` (a CLIP model directory; ``clip_max_tokens``: `CLIPScorer`'s
+    ``max_tokens``, 64 unless ViT-B/16, L/14 or CLIP's own text context of 77 is wanted), from the caption strings of the
     batches (SENT captions, or WORD captions through the dataset's ``i2w``; 'clip_score_*' in ``metrics``).  With ``org_dir`` the real side is cached beside it.  Every score is logged (or one
     line says why there is none), written to ``writer`` and, FID apart, put into ``metrics`` when a dict is passed ('k' of PRDC as 'prdc_k';
     of KID and IS every name but 'kid' / 'inception_score' carries that word as a prefix: 'kid_std', 'kid_n_real', 'inception_score_n', ...).  Returns (uint8 tensor of the generated images,
@@ -893,7 +902,7 @@ def eval(loader, state_epoch, text_encoder, netG, logger, num_samples=6000, save
     suite = MetricSuite(device, fid_inception or given.fid_inception or os.environ.get('XMC_FID_INCEPTION', ''),
                         given.prdc_k if prdc is None else prdc,
                         damsm_image_encoder or given.damsm_image_encoder or os.environ.get('XMC_DAMSM_IMAGE_ENCODER', ''), text_encoder,
-                        **_new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score), **({'clip_dir': clip_dir} if clip_dir else {}))
+                        **_new_metric_args(given, kid, kid_subsets, kid_subset_size, inception_score), **({'clip_dir': clip_dir, **_clip_tokens_arg(clip_max_tokens)} if clip_dir else {}))
     if org_dir:
         suite.open_cache(os.path.dirname(os.path.abspath(org_dir)))
     cnt, outs = 0, []
@@ -1059,6 +1068,8 @@ def _checked_args(argv):
                             resolve_weights(args.damsm_image_encoder, 'XMC_DAMSM_IMAGE_ENCODER', '--damsm_image_encoder', must_exist=False),
                             args.kid, args.kid_subsets, args.kid_subset_size, args.inception_score)
     args.clip_dir = args.clip_dir or os.environ.get('XMC_CLIP_DIR', '')
+    if not 64 <= args.clip_max_tokens <= 1024:
+        raise SystemExit(f'--clip_max_tokens: {args.clip_max_tokens} is outside [64, 1024]')
     if args.clip_dir and not os.path.isfile(os.path.join(args.clip_dir, 'config.json')):
         raise SystemExit(f'--clip_dir: {args.clip_dir} is not a CLIP model directory (no config.json)')
     return args, aug_policy, eval_opts
@@ -1153,7 +1164,8 @@ def main(argv=None):
                  netG=netG, netD=netD, optimizerG=optimizerG, optimizerD=optimizerD, logger=logger, model_dir=model_dir,
                  opts=StepOptions(gather_negatives=args.gather_negatives, graph=bool(args.graph), log_each_step=bool(args.log_each_step),
                                   ema=ema, diffaug=aug, vgg=vgg, vgg_smooth=args.vgg_smooth),
-                 img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts, clip_dir=args.clip_dir or None)
+                 img_dir=img_dir if rank == 0 else None, writer=writer, eval_opts=eval_opts, clip_dir=args.clip_dir or None,
+                 **_clip_tokens_arg(args.clip_max_tokens))
     if writer is not None:
         writer.close()
     torch.cuda.synchronize()
